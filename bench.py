@@ -7,7 +7,7 @@ configs[2], the config the metric is quoted on); weak scaling: every rank owns 4
 Inputs (state, items, pre-generated U(-1,1) actions) are resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096]
-                    [--kind gather|flat|maze|point|maze_mj|flagrun|mixed] [--backend nccl|gloo]
+                    [--kind gather|flat|maze|point|maze_mj|flagrun|mixed] [--backend nccl|gloo] [--full] [--dump-outputs DIR]
 
 `--kind mixed` is BASELINE.json configs[4] per GPU: the first half of the shard AntGather, the second half PointGather
 (two hrl_step launches per step on two HIP streams, so the kernels overlap on the chip), one JSON line.
@@ -15,7 +15,10 @@ Inputs (state, items, pre-generated U(-1,1) actions) are resident in HBM before 
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) BEFORE anything touches
 the GPU, passes their output through and exits with their status.  Under torch.distributed.run it is a rank.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, settles, warms up, times the K steps and prints the
+headline; `--full` adds what takes work of its own: the `roofline` object (HIP-event kernel time + committed counters), the solver-row regime
+(an untimed pass after the window), a finite-state check and the `cpu_baseline` object (unless --no-cpu-baseline).
+`--dump-outputs DIR`: after the timed region, what the last timed step returned (obs, reward, done, info) as DIR/<name>.npy, float32.
 """
 import argparse
 import ctypes as C
@@ -40,6 +43,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MAX_CLOCK_GHZ = 2.4     # MI355X_MICROARCH.md chip table
 N_SIMD = 256 * 4        # 256 CUs x 4 SIMD-32
 VALU_ISSUE_CYCLES = 2   # a wave64 VALU instruction occupies its SIMD-32 for 2 cycles
+DUMP_LIMIT_BYTES = 60 << 20   # --dump-outputs: array data of one run, all ranks together (under 64 MB with the .npy headers)
 
 
 def parse_args():
@@ -59,7 +63,13 @@ def parse_args():
     ap.add_argument('--watchdog', type=float, default=900.0, help='seconds a rank may go WITHOUT PROGRESS (a new stage, or another 64 launches queued) before '
                     'it reports the stage it hangs in and exits 3 (0 = off)')
     ap.add_argument('--stall-in', default=None, help=argparse.SUPPRESS)  # test hook: sleep forever on entering this stage (tests/test_gpu_envs.py)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also roofline, solver-row regime, finite-state check and CPU baseline (off: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned as DIR/<name>.npy (float32, '
+                    f'at most {DUMP_LIMIT_BYTES >> 20} MiB in all: a fixed, seeded sample of env rows beyond that)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 class Watchdog:
@@ -223,6 +233,33 @@ def reference_probe():
     return {'value': n / (time.perf_counter() - t0), 'unit': 'env-steps/s', 'cores': 1, 'kind': 'reference'}  # pragma: no cover
 
 
+def step_outputs(ret, prefix=''):
+    """{name: tensor} of what one BatchedEnv.step() returned -- (obs, reward, done, info) -- under flat file names."""
+    obs, rew, done, info = ret
+    out = {prefix + 'obs': obs, prefix + 'reward': rew, prefix + 'done': done}
+    for k, v in info.items():
+        out[prefix + 'info_' + k.replace('.', '_')] = v
+    return out
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Writes {name: array} as out_dir/<name>.npy: float64 stays float64, everything else becomes float32.  Dimension 0 of every array is the
+    env; when the arrays hold more than `limit` bytes in all, each keeps the same share of its rows, a sorted sample drawn with a fixed seed
+    (arrays with equally many rows keep the same rows), so that two runs with the same arguments write the same elements."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        for k, v in arrays.items():
+            keep = max(1, v.shape[0] * limit // total)
+            arrays[k] = v[np.sort(np.random.RandomState(0).choice(v.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(v))
+    return arrays
+
+
 def pmc_summary(kind):
     """Committed rocprofv3 PMC summary of k_step<kind> (profiles/pmc_summary.json, tools/summarize_profile.py).
     bench.py cannot collect counters itself; {} when no summary for this kernel is committed."""
@@ -330,11 +367,13 @@ def main():
     gather_phase = gather_every // 2   # launched in the MIDDLE of its interval: a collective queued behind the window's last step would be waited for, exposed, by the
     #                                    synchronisation that ends the window (one all-gather latency in a 20-launch window); queued mid-window it overlaps the steps that follow
 
+    last = [None] * len(envs)   # what each env's latest step() returned (views of its output tensors): --dump-outputs
+
     def run(k0, k):
         for t in range(k0, k0 + k):
-            for _, env, acts, stream in envs:
+            for i, (_, env, acts, stream) in enumerate(envs):
                 with torch.cuda.stream(stream):
-                    env.step(acts[t % T])
+                    last[i] = env.step(acts[t % T])
             if gatherer is not None and (t + 1) % gather_every == gather_phase:
                 gatherer.launch()
             if (t & 63) == 63:
@@ -356,7 +395,8 @@ def main():
         torch.distributed.barrier()
         torch.cuda.synchronize(dev)
     wd.at('timed region')
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in envs]  # made before the clock starts (hipEventCreate is host time, not step time)
+    # --full: HIP events for the roofline's kernel time, made before the clock starts (hipEventCreate is host time, not step time)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in envs] if args.full else []
     t0 = time.perf_counter()
     # HIP events on the stream each kernel is launched on, around launches 2..K of the timed region: an event recorded on an IDLE stream is
     # stamped at once and the first launch arrives ~20 us later (host-to-GPU dispatch latency) -- in the driver's 20-launch window that would add
@@ -375,14 +415,21 @@ def main():
         torch.distributed.barrier()
     wall = time.perf_counter() - t0       # the contract's bracket: barrier + synchronize on both sides (`value`); the closing barrier itself -- an all-reduce and
     #                                       a synchronisation -- is in it, `ms_per_step_before_barrier` shows the steps without it
+    if args.dump_outputs:   # before anything launches again: the returned tensors are the env's own, overwritten by the next step
+        wd.at('dump outputs')
+        named = {}
+        for (kname, _, _, _), ret in zip(envs, last):
+            named.update(step_outputs(ret, (f'rank{rank}_' if world > 1 else '') + (f'{kname}_' if len(envs) > 1 else '')))
+        dump_outputs({k: v.cpu().numpy() for k, v in named.items()}, args.dump_outputs, DUMP_LIMIT_BYTES // world)
     wd.at('reductions after the timed region')
     dev_ms = [e0.elapsed_time(e1) for e0, e1 in ev]
     if world > 1:
         tt = torch.tensor([wall, wall_own], device=dev if torch.distributed.get_backend() == 'nccl' else 'cpu', dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         wall, wall_own = float(tt[0].item()), float(tt[1].item())
-    for _, env, _, _ in envs:
-        assert bool(torch.isfinite(env.state).all()), 'non-finite state after the timed region'
+    if args.full:
+        for _, env, _, _ in envs:
+            assert bool(torch.isfinite(env.state).all()), 'non-finite state after the timed region'
     gathered_ok = None
     rccl = None
     if gatherer is not None:
@@ -401,16 +448,17 @@ def main():
                 'collective': 'all_gather_into_tensor of the episode returns on a side stream, off the step path'}
     # solver rows per env: the regime the launch time belongs to, in the line itself.  Counted in an UNTIMED pass over the launches that follow the window
     # (the counter is a per-env read-modify-write the shipped configuration does not do, so it is not bound inside the window; the regime is the settled
-    # one either way: an env's row count persists from step to step).  No collective in it.
+    # one either way: an env's row count persists from step to step).  No collective in it.  --full only.
     rows_steps = max(1, min(args.steps, 200))
-    for _, env, _, _ in envs:
-        env.count_solver_rows()
-    t_rows = args.settle + args.warmup + args.steps
-    for t in range(t_rows, t_rows + rows_steps):
-        for _, env, acts, stream in envs:
-            with torch.cuda.stream(stream):
-                env.step(acts[t % T])
-    torch.cuda.synchronize(dev)
+    if args.full:
+        for _, env, _, _ in envs:
+            env.count_solver_rows()
+        t_rows = args.settle + args.warmup + args.steps
+        for t in range(t_rows, t_rows + rows_steps):
+            for _, env, acts, stream in envs:
+                with torch.cuda.stream(stream):
+                    env.step(acts[t % T])
+        torch.cuda.synchronize(dev)
     if world > 1:  # all collectives are done: leave the group before rank 0 spends ~25 s of host time on the CPU baseline
         wd.at('final barrier')
         torch.distributed.barrier()
@@ -422,7 +470,6 @@ def main():
         # dominant kernel: the ant step (for mixed: k_step<gather> over its half of the shard, overlapped with the point kernel)
         dom = 0
         dom_kind, dom_env = envs[dom][0], envs[dom][1]
-        launch_s = dev_ms[dom] / 1e3 / (args.steps - first)  # one kernel per step per stream: HIP-event time on that stream / the launches between the events
         if args.kind == 'gather' and n == 4096:
             metric = 'env-steps/sec, AntGatherBulletEnv-v0 @4096 envs, 1/2/4/8 MI355X'
         elif args.kind == 'mixed':
@@ -440,13 +487,6 @@ def main():
             # True: at least 200 untimed steps (settle + warmup) lie between the reset and the timed window -- the ants stand, the contact count and
             # with it the launch time have levelled off (launches are ~5 % shorter in the first 50 steps after a reset)
             'steady_state': args.settle + args.warmup >= 200, 'settle_steps': args.settle,
-            # mean constraint rows per env and env step (joint limits + 3 per contact, summed over the 4 substeps) over the `solver_rows_steps` untimed launches
-            # right after the timed window: the sweeps are serial in the rows, so this is the regime the launch time belongs to (hrl_buffers.solver_rows)
-            'solver_rows_per_env_step': {k: float(env.solver_rows.sum().item()) / (env.num_envs * rows_steps) for k, env, _, _ in envs},
-            # the env with the most rows: a launch lasts as long as its slowest env's chain (one env of 4096 that lies against a wall with 12
-            # contacts, 23 rows per substep instead of 20, makes every launch 3 - 4 us longer)
-            'solver_rows_max_env': {k: float(env.solver_rows.max().item()) / rows_steps for k, env, _, _ in envs},
-            'solver_rows_steps': rows_steps,
             'config': {'workload': f'{shard}, U(-1,1) actions pre-generated on device, auto-reset, max_episode_steps 2000',
                        'envs_per_gpu': n, 'global_envs': world * n,
                        'substeps_per_step': 4,
@@ -454,17 +494,26 @@ def main():
                        'parallelism': 'one GPU, one process, no collective' if world == 1 else
                                       f'env-sharded x{world} (one process per GPU), no data-path collective; all-gather of episode returns '
                                       f'every {gather_every} steps on a side stream (see `rccl`)'},
-            'roofline': roofline(dom_kind, dom_env.num_envs, launch_s),
         }
+        if args.full:
+            # mean constraint rows per env and env step (joint limits + 3 per contact, summed over the 4 substeps) over the `solver_rows_steps` untimed launches
+            # right after the timed window: the sweeps are serial in the rows, so this is the regime the launch time belongs to (hrl_buffers.solver_rows)
+            out['solver_rows_per_env_step'] = {k: float(env.solver_rows.sum().item()) / (env.num_envs * rows_steps) for k, env, _, _ in envs}
+            # the env with the most rows: a launch lasts as long as its slowest env's chain (one env of 4096 that lies against a wall with 12
+            # contacts, 23 rows per substep instead of 20, makes every launch 3 - 4 us longer)
+            out['solver_rows_max_env'] = {k: float(env.solver_rows.max().item()) / rows_steps for k, env, _, _ in envs}
+            out['solver_rows_steps'] = rows_steps
+            launch_s = dev_ms[dom] / 1e3 / (args.steps - first)  # one kernel per step per stream: HIP-event time on that stream / the launches between the events
+            out['roofline'] = roofline(dom_kind, dom_env.num_envs, launch_s)
+            if args.kind == 'mixed':
+                out['roofline']['streams_ms_per_step'] = {k: ms / (args.steps - first) for (k, _, _, _), ms in zip(envs, dev_ms)}
         if world > 1:   # the slowest rank's own K steps, before the barrier that closes the timed bracket (that barrier is inside `value` / `ms_per_step`)
             out['ms_per_step_before_barrier'] = wall_own / args.steps * 1e3
-        if args.kind == 'mixed':
-            out['roofline']['streams_ms_per_step'] = {k: ms / (args.steps - first) for (k, _, _, _), ms in zip(envs, dev_ms)}
         if gathered_ok is not None:
             out['config']['returns_gathered_ok'] = gathered_ok
         if rccl is not None:
             out['rccl'] = rccl
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg belongs to the N = 1 line only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg belongs to the N = 1 line only
             out['cpu_baseline'] = cpu_baseline(args.kind)
         print(json.dumps(out), flush=True)
     wd.done()

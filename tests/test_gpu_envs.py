@@ -358,7 +358,7 @@ def _bench_line(args, timeout=600):
 
 def test_bench_mixed_kind_one_gpu():
     """BASELINE.json configs[4] per GPU through bench.py: one JSON line, both sub-shards stepped on their own streams."""
-    out = _bench_line(['--kind', 'mixed', '--envs', '4096', '--steps', '30', '--warmup', '5', '--no-cpu-baseline'])
+    out = _bench_line(['--kind', 'mixed', '--envs', '4096', '--steps', '30', '--warmup', '5', '--no-cpu-baseline', '--full'])
     assert 'mixed batch' in out['metric'] and out['n_gpus'] == 1 and out['config']['envs_per_gpu'] == 4096
     assert out['value'] > 1e6 and out['roofline']['kernel'] == 'k_step<gather>'
     assert set(out['roofline']['streams_ms_per_step']) == {'gather', 'point'}
@@ -413,7 +413,7 @@ def test_bench_four_ranks_of_the_config5_shape():
     ranks + this one): `--gpus 4 --kind mixed` over gloo, every rank half AntGather half PointGather on two streams, the ReturnGatherer
     gathering both halves of all four shards.  The line proves what ran: world size, every rank seen, the collectives of the timed region."""
     out = _bench_line(['--gpus', '4', '--backend', 'gloo', '--kind', 'mixed', '--envs', '64', '--steps', '20', '--warmup', '5', '--settle', '20',
-                       '--gather-every', '5', '--no-cpu-baseline'])
+                       '--gather-every', '5', '--no-cpu-baseline', '--full'])
     assert out['n_gpus'] == 4 and out['config']['global_envs'] == 256 and 'mixed batch' in out['metric']
     r = out['rccl']
     assert r['world_size'] == 4 and r['ranks_seen'] == [0, 1, 2, 3] and len(r['devices']) == 4 and r['gather_count'] == 4 and r['gather_bytes_per_rank'] == 4 * 64
@@ -424,12 +424,43 @@ def test_bench_default_line_is_a_steady_state_line():
     """Whatever the driver passes for --warmup, the timed window starts 300 untimed steps after the reset (--settle): `steady_state` is true, and
     the line carries the regime it was measured in -- the mean solver rows per env step (a standing ant: four feet on the ground and a few joints
     near their stops: ~50 rows over four substeps; just after a reset: fewer)."""
-    out = _bench_line(['--steps', '20', '--warmup', '5', '--no-cpu-baseline'])   # the driver's flags
+    out = _bench_line(['--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--full'])   # the driver's flags (+ --full: the solver-row pass)
     assert out['steady_state'] is True and out['settle_steps'] == 300 and out['warmup'] == 5 and out['steps'] == 20
     rows = out['solver_rows_per_env_step']['gather']
     assert 30 < rows < 120, rows
-    cold = _bench_line(['--steps', '20', '--warmup', '5', '--settle', '0', '--no-cpu-baseline'])
+    cold = _bench_line(['--steps', '20', '--warmup', '5', '--settle', '0', '--no-cpu-baseline', '--full'])
     assert cold['steady_state'] is False and cold['solver_rows_per_env_step']['gather'] < rows
+
+
+def test_bench_plain_line_and_dumped_outputs_of_the_last_timed_step(tmp_path):
+    """A plain run (no --full) prints the headline only, times exactly --steps steps, and --dump-outputs writes what the LAST timed step returned:
+    the same arrays as a replay of the same settle + warmup + timed steps (same config, same seeded actions) in this process, and the same
+    files from a second run."""
+    from hrl_pybullet_envs_amd import _lib
+    from hrl_pybullet_envs_amd.vec_env import BatchedEnv
+    n, settle, warmup, steps = 256, 10, 3, 7
+    args = ['--envs', str(n), '--settle', str(settle), '--warmup', str(warmup), '--steps', str(steps)]
+    out = _bench_line(args + ['--dump-outputs', str(tmp_path / 'a')])
+    assert out['steps'] == steps and out['ms_per_step'] > 0 and abs(out['value'] - n / (out['ms_per_step'] / 1e3)) < 1e-6 * out['value']
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype'} <= set(out) and out['unit'] == 'env-steps/s' and out['dtype'] == 'f32'
+    assert not {'roofline', 'cpu_baseline', 'solver_rows_per_env_step'} & set(out)
+    _bench_line(args + ['--dump-outputs', str(tmp_path / 'b')])
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert {'obs.npy', 'reward.npy', 'done.npy', 'info_episode_return.npy'} <= set(names) and names == sorted(p.name for p in (tmp_path / 'b').iterdir())
+    dumped = {nm[:-4]: np.load(tmp_path / 'a' / nm) for nm in names}
+    for nm, v in dumped.items():
+        assert v.dtype == np.float32 and np.array_equal(v, np.load(tmp_path / 'b' / f'{nm}.npy')), nm
+    dev = torch.device('cuda', 0)
+    env = BatchedEnv(_lib.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=0, auto_reset=1, env_id_offset=0), dev)
+    env.reset()
+    acts = torch.rand(256, n, env.act_dim, device=dev, generator=torch.Generator(device=dev).manual_seed(0)) * 2 - 1   # bench.py's actions, rank 0
+    for t in range(settle + warmup + steps):
+        obs, rew, done, info = env.step(acts[t % 256])
+    torch.cuda.synchronize()
+    assert np.array_equal(dumped['obs'], obs.cpu().numpy()) and np.array_equal(dumped['reward'], rew.cpu().numpy())
+    assert np.array_equal(dumped['done'], done.cpu().numpy().astype(np.float32))
+    assert np.array_equal(dumped['info_episode_return'], info['episode_return'].cpu().numpy())
+    env.close()
 
 
 def test_bench_watchdog_names_the_stage_a_rank_hangs_in():

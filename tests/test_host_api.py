@@ -152,12 +152,16 @@ def test_gymnasium_adapter_five_tuple():
     assert o[4][2].tolist() == [True, False] and o[4][3].tolist() == [False, False]
 
 
-def test_bench_spawns_its_own_ranks(monkeypatch):
+def test_bench_spawns_its_own_ranks(tmp_path, monkeypatch):
     """bench.py --gpus N without WORLD_SIZE starts the N ranks itself (torch.distributed.run on 127.0.0.1) before it
     imports anything that could touch the GPU, and hands back their exit status."""
     import importlib
     import bench
     importlib.reload(bench)
+    _fake_kfd(tmp_path, [0, 1024, 1024, 1024, 1024])   # a machine with the four GPUs asked for, whatever this host has (preflight)
+    monkeypatch.setenv('HRL_KFD_ROOT', str(tmp_path))
+    for var in ('ROCR_VISIBLE_DEVICES', 'HIP_VISIBLE_DEVICES', 'CUDA_VISIBLE_DEVICES'):
+        monkeypatch.delenv(var, raising=False)
     calls = {}
 
     def fake_call(cmd, env=None):
@@ -187,6 +191,27 @@ def test_bench_roofline_reports_hbm_and_valu(monkeypatch):
     v = r['valu']
     assert v['issue_cycles_per_simd'] == v['insts_per_env'] * 4096 / 1024 * 2
     assert 0 < v['frac'] < v['frac_at_held_clock'] < 1
+
+
+def test_bench_dump_outputs_float_files_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32 (float64 kept); over the byte limit every array keeps the same share of its
+    rows, the same rows for arrays of equal length, and the same rows from run to run."""
+    import bench
+    rng = np.random.RandomState(1)
+    arrays = {'obs': rng.rand(1000, 30).astype(np.float32), 'done': (rng.rand(1000) < 0.5).astype(np.uint8), 'ret64': rng.rand(1000)}
+    bench.dump_outputs(arrays, str(tmp_path / 'all'))
+    for k, v in arrays.items():
+        got = np.load(tmp_path / 'all' / f'{k}.npy')
+        assert got.dtype == (np.float64 if k == 'ret64' else np.float32) and np.array_equal(got, v)
+    limit = sum(v.nbytes for v in arrays.values()) // 4    # done as float32 counts 4 B per row
+    for d in ('a', 'b'):
+        bench.dump_outputs(arrays, str(tmp_path / d), limit=limit)
+    out = {k: np.load(tmp_path / 'a' / f'{k}.npy') for k in arrays}
+    assert sum(v.nbytes for v in out.values()) <= limit and 0 < len(out['obs']) < 1000
+    rows = [int(np.flatnonzero((arrays['obs'] == r).all(1))[0]) for r in out['obs']]
+    assert rows == sorted(rows) and np.array_equal(out['ret64'], arrays['ret64'][rows]) and np.array_equal(out['done'], arrays['done'][rows])
+    for k in arrays:
+        assert np.array_equal(out[k], np.load(tmp_path / 'b' / f'{k}.npy'))
 
 
 def test_default_config_rejects_unknown_fields():
