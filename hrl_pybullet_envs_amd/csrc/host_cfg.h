@@ -144,7 +144,7 @@ inline std::string validate(const hrl_config *c) {
     if (m.max_contacts < 1 || m.max_contacts > MAXC) return "model.max_contacts must be within 1..12";
     if (!(m.linear_damping >= 0) || !(m.angular_damping >= 0) || !(m.restitution >= 0) || !(m.restitution_threshold >= 0) || !(m.joint_damping >= 0) || !(m.joint_armature >= 0))
         return "model damping / restitution / armature parameters must be >= 0";
-    if (m.step_group != 0 && m.step_group != 1) return "model.step_group must be 0 (four env-waves per workgroup) or 1 (one wave per env)";
+    if (m.step_group != 0 && m.step_group != 1) return "model.step_group must be 0 or 1 (both launch four env-waves per workgroup)";
     return "";
 }
 

@@ -37,16 +37,17 @@ namespace {
 thread_local std::string g_err;
 unsigned long long *g_stamps = nullptr; /* set only by the diagnostic entry point hrl_debug_set_stamps */
 
-/* G = envs (= waves) per workgroup.  G = 1: one 64-thread workgroup per env, every phase on the env's own wave.  G = 4: four
- * env-waves share a 256-thread workgroup and the lane-sparse phases of all four run once on wave 0 (step_core.h,
- * ant_group_block); phases of one wave are ordered by a wave-level LDS fence, the two blocks of a substep by s_barrier. */
+/* G = envs (= waves) per workgroup.  G = 1: one 64-thread workgroup per env, every phase on the env's own wave (the point bot's step,
+ * reset, observe and the goal kernels).  G = 4 (the ant kinds' step): four env-waves share a 256-thread workgroup and the lane-sparse
+ * phases of all four run once on wave 0 (step_core.h, ant_group_block); phases of one wave are ordered by a wave-level LDS fence, the
+ * two blocks of a substep by s_barrier. */
 template <int G>
 struct GpuExec {
     WaveLds *Ls; /* the group's records, [G] */
     LaneRegs r;
     int lane, wave;
     __device__ __forceinline__ WaveLds &lds() { return Ls[G == 1 ? 0 : wave]; }
-    __device__ __forceinline__ WaveLds &lds(int k) { return Ls[G == 1 ? 0 : k]; }
+    __device__ __forceinline__ WaveLds &lds(int k) { return Ls[k]; } /* record k of the group (G = 4 only) */
     __device__ __forceinline__ LaneRegs &reg(int) { return r; }
     /* orders this wave's LDS writes before its later LDS reads (the lanes of a wave exchange data through LDS) */
     __device__ __forceinline__ void wave_sync() {
@@ -54,14 +55,13 @@ struct GpuExec {
         else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
     }
     __device__ __forceinline__ void group_sync() { if (G > 1) __syncthreads(); }
-    /* a phase of the group block: executed by the leader wave, lane >> 4 = env of the group */
+    /* a phase of the group block: executed by the leader wave, lane >> 4 = env of the group (G = 4 only) */
     template <class F>
     __device__ __forceinline__ void leader(F f) {
-        if (G == 1 || wave == 0) { f(lane); wave_sync(); }
+        if (wave == 0) { f(lane); wave_sync(); }
     }
     __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
     __device__ __forceinline__ int wave_index() const { return __builtin_amdgcn_readfirstlane(wave); }
-    static constexpr __device__ __forceinline__ int group_size() { return G; }
     /* Makes the lane id (and the friction links) opaque to the optimizer at this point.  Without it every
      * lane-derived value of the unrolled solver (44 `lane == r` masks, LDS addresses, ...) is loop-invariant, gets
      * hoisted to the top of the kernel and is spilled to scratch for the whole substep loop. */
@@ -226,21 +226,15 @@ __global__ __launch_bounds__(64, 4) void k_set_goals(DevBufs b, const DevCfg *__
     set_goals_entry(x, b, *cp, xcd_group(), goals_xy, n_goals, ok);
 }
 using kernel_fn = void (*)(DevBufs, const DevCfg *);
-/* group = envs per workgroup of the step kernel: 4 for the ant kinds (1 selectable for A/B measurements), 1 for the point bot */
-kernel_fn step_kernel(int kind, int group) {
-    if (group == 4) switch (kind) {
+/* envs per workgroup of the step kernel: 4 for the ant kinds, 1 for the point bot */
+int step_group(int kind) { return kind == HRL_POINT_GATHER ? 1 : 4; }
+kernel_fn step_kernel(int kind) {
+    switch (kind) {
         case HRL_ANT_FLAT: return k_step<HRL_ANT_FLAT, 4>;
         case HRL_ANT_GATHER: return k_step<HRL_ANT_GATHER, 4>;
         case HRL_ANT_MAZE: return k_step<HRL_ANT_MAZE, 4>;
         case HRL_ANT_MAZE_MJ: return k_step<HRL_ANT_MAZE_MJ, 4>;
         case HRL_ANT_FLAGRUN: return k_step<HRL_ANT_FLAGRUN, 4>;
-    }
-    switch (kind) {
-        case HRL_ANT_FLAT: return k_step<HRL_ANT_FLAT, 1>;
-        case HRL_ANT_GATHER: return k_step<HRL_ANT_GATHER, 1>;
-        case HRL_ANT_MAZE: return k_step<HRL_ANT_MAZE, 1>;
-        case HRL_ANT_MAZE_MJ: return k_step<HRL_ANT_MAZE_MJ, 1>;
-        case HRL_ANT_FLAGRUN: return k_step<HRL_ANT_FLAGRUN, 1>;
         default: return k_step<HRL_POINT_GATHER, 1>;
     }
 }
@@ -304,7 +298,6 @@ struct hrl_handle {
     DevCfg dc;
     DevCfg *d_dc; /* device copy of the constants (the only device memory the library owns) */
     int device;   /* the device that was current at hrl_create(): d_dc lives there, and so must the caller's buffers */
-    int group;    /* envs per workgroup of the step kernel */
 };
 
 namespace {
@@ -347,8 +340,6 @@ int hrl_create(const hrl_config *cfg, hrl_handle **out) {
     h->cfg = *cfg;
     build_devcfg(*cfg, h->dc);
     h->d_dc = nullptr;
-    h->group = cfg->env_kind == HRL_POINT_GATHER ? 1 : 4;
-    if (cfg->model.step_group == 1) h->group = 1; /* measurement reference: the one-wave-per-env launch (hrl_model.step_group) */
     hipError_t e2 = hipGetDevice(&h->device);
     if (e2 == hipSuccess) e2 = hipMalloc((void **)&h->d_dc, sizeof(DevCfg));
     if (e2 == hipSuccess) e2 = hipMemcpy(h->d_dc, &h->dc, sizeof(DevCfg), hipMemcpyHostToDevice);
@@ -386,7 +377,6 @@ int hrl_update_config(hrl_handle *h, const hrl_config *cfg, void *stream) {
     const hipError_t e = hipMemcpyAsync(h->d_dc, &dc, sizeof(DevCfg), hipMemcpyHostToDevice, (hipStream_t)stream); /* pageable source: staged before the call returns */
     if (e != hipSuccess) return hip_fail(e, "hrl_update_config: device constants");
     h->cfg = *cfg; h->dc = dc;
-    h->group = cfg->env_kind == HRL_POINT_GATHER || cfg->model.step_group == 1 ? 1 : 4;
     return HRL_OK;
 }
 
@@ -408,8 +398,8 @@ int hrl_step(hrl_handle *h, const hrl_buffers *b, void *stream) {
     if (const int rc = check_call(h, b, "hrl_step")) return rc;
     if (!b->state || !b->aux || !b->obs || !b->actions || !b->reward || !b->done || !b->info) return fail(HRL_ERR_BAD_ARG, "hrl_step: null buffer");
     if (needs_items(h->dc) && !b->items) return fail(HRL_ERR_BAD_ARG, std::string("hrl_step: ") + items_why);
-    const int G = h->group;
-    hipLaunchKernelGGL(step_kernel(h->dc.kind, G), dim3((h->dc.n_envs + G - 1) / G), dim3(64 * G), 0, (hipStream_t)stream, to_dev(b, nullptr), (const DevCfg *)h->d_dc);
+    const int G = step_group(h->dc.kind);
+    hipLaunchKernelGGL(step_kernel(h->dc.kind), dim3((h->dc.n_envs + G - 1) / G), dim3(64 * G), 0, (hipStream_t)stream, to_dev(b, nullptr), (const DevCfg *)h->d_dc);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? HRL_OK : hip_fail(e, "hrl_step launch");
 }

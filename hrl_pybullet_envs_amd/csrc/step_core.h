@@ -12,9 +12,9 @@
  * written as a sequence of wave-wide PHASES.  A phase is a function of (lane, LDS); lanes communicate only
  * through the per-wave LDS record `WaveLds` between phases (plus the wave primitives supplied by the executor:
  * a ballot/prefix compaction, a solver-row lane broadcast, a lane shuffle and per-lane persistent registers).  The executor `X`
- * is the HIP wave (hrl_hip.hip: one 64-thread workgroup = one wavefront = one env, phases separated by a
- * workgroup barrier); tests/emu provides a lock-step host executor so the same phases can be checked on a box
- * without a GPU -- that executor is test infrastructure and is never used by the product.
+ * is the HIP wave (hrl_hip.hip: one wavefront = one env, four env-waves per workgroup for the ant kinds, phases separated by
+ * wave-level LDS fences and the substep's blocks by workgroup barriers); tests/emu provides a lock-step host executor so the
+ * same phases can be checked on a box without a GPU -- that executor is test infrastructure and is never used by the product.
  *
  * Lane maps used by the phases:
  *   body map: lane >> 2 = rigid body (0-3 feet, 4-7 aux bodies, 8.. torso): phases K1, K2, B; the lanes of a group compute the same values
@@ -164,14 +164,15 @@ struct alignas(16) WaveLds {
     int ljoint[NJ];
     float lsign[NJ], ldist[NJ];
     int gtouch[16];
-    int nC, nL, nS, on; /* contacts / limit rows / self contacts found by ant_contacts for this env's substep; on = the record holds an env */
+    int nC, nL, nS, on; /* contacts / limit rows / self contacts found by ant_contacts_group / ant_limits_group for this env's substep;
+                           on = the record holds an env (no reader: dropping it would move every field behind it) */
     int ncnt;           /* ant_contacts_group: contacts a packed pass found for this env (added to nC by the next phase) */
     float planes[4][4];  /* lateral half-spaces (n, d), copied from the constants when the env is loaded: the collision passes index them per lane */
     /* (at the END of the record: in the middle, behind csurf, the same two arrays made every launch 0.4 us longer -- they shift the solver's arrays against the LDS banks) */
     float ct[MAXC];      /* contacts of a capsule with a box / cube: the parameter of the contact's point on the capsule's axis (read by second_support) */
     int csph[MAXC];      /* the shape that touches: 0 the torso sphere, 1..12 the capsule that ends in sphere s; -1: a capsule pair */
 #ifdef HRL_WGTIME
-    int dbg_rows; /* diagnostic build (tools/wg_times.py): solver rows | cube passes << 16 | self-contact substeps << 24, summed over the step */
+    int dbg_rows; /* diagnostic build (tools/wg_times.py): solver rows | self-contact substeps << 24, summed over the step */
 #endif
 };
 
@@ -487,7 +488,7 @@ HRL_DEV void phase_kin_ankle(const DevCfg &c, WaveLds &L, LaneRegs &g, const flo
     if (type != 0) return; /* aux body: continues in K2; torso: in B */
     /* one destination at a time: stores to consecutive addresses that follow each other merge into wide LDS writes */
     /* (the leg points ph / pa / tip are not published here: their only readers, the collision passes and the parts centroid, take
-     * them from a POS_ONLY pass of their own -- ant_contacts runs on another wave at the same time as this phase) */
+     * them from a POS_ONLY pass of their own -- ant_contacts_group runs on another wave at the same time as this phase) */
 #pragma unroll
     for (int k = 0; k < 6; ++k) L.S[jh][k] = Sh[k];
 #pragma unroll
@@ -497,24 +498,8 @@ HRL_DEV void phase_kin_ankle(const DevCfg &c, WaveLds &L, LaneRegs &g, const flo
 #pragma unroll
     for (int k = 0; k < 6; ++k) L.cb[ja][k] = cba[k];
     float Ua[6], Iac[6];
-#ifdef HRL_VAR_LEAF_CLOSED_FORM /* A/B build only (profiles/EXPERIMENTS.md 9.a): the ankle's U = I S and D = S . U of the LEAF body in closed form -- the foot is rigid and its
-                                   joint axis is fixed in it and perpendicular to its own axis, so U = [alpha w + c x (m d (w x e)); m d (w x e)] and D = alpha + m d^2 is a
-                                   constant: what "joint axes with a zero linear part" buys for this joint without any shift of inertias.  Not the specification (other roundings). */
-    {
-        float tt[3], lin[3], cl[3];
-        const float dd = c.L2 * 0.5f, md = m2 * dd;
-        cross3(tt, axw, e2);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lin[k] = md * tt[k];
-        cross3(cl, cfoot, lin);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { Ua[k] = fma_(a2_, axw[k], cl[k]); Ua[3 + k] = lin[k]; }
-    }
-    const float invDa = 1.f / (fma_(m2 * (c.L2 * 0.5f), c.L2 * 0.5f, a2_) + c.armature);
-#else
     sym6_matvec(Ua, If, Sa);
     const float invDa = 1.f / (dot6(Sa, Ua) + c.armature);             /* + 0 at the default: the same bits */
-#endif
     const float uta = fma_(-c.jdamp, qda, L.tau[ja]) - dot6(Sa, pAf);   /* - 0 * rate at the default: the same bits */
 #pragma unroll
     for (int a = 0; a < 6; ++a)
@@ -1306,8 +1291,6 @@ HRL_DEV void pgs_solve(X &x, const DevCfg &c, int nL, int nC, bool ant, bool sel
  * Block 2 (ant_env_block), on every env's own wave: rows, A, sweeps, velocity reconstruction (up to 44 rows of distinct
  * work), then the position integration.
  * Inside a block the phases of a wave are separated by wave-level LDS synchronisation only.
- * With a group of one (executor G = 1) the only wave does all of it in order, the four 16-lane slices of the group block
- * computing the same values on the same record: the one-wave-per-env form.
  * qi = index of the position buffer the substep works on; its integration writes q[qi ^ 1]. */
 template <class X>
 HRL_DEV void ant_group_block(X &x, const DevCfg &c, int qi) {
@@ -1336,169 +1319,25 @@ HRL_DEV void store_contact(WaveLds &L, int i, const Hit &h, bool up, bool on_box
     }
 }
 
-/* Contacts and limit rows of ONE env's pose q[qi] into its record L -- executed by whichever wave has the time: it needs the pose
- * only (the leg points come from a POS_ONLY kinematics pass of its own), so it runs WHILE the leader wave works through the group
- * block, on the waves that would otherwise wait at the barrier.  Results: the contact / limit lists and L.nC / nL / nS. */
-template <class X>
-HRL_DEV void ant_contacts(X &x, const DevCfg &c, WaveLds &L, int qi, bool items_on) {
-    const float *q = L.q[qi];
-    const int cap = c.max_contacts; /* contacts kept per substep (hrl_model.max_contacts <= MAXC) */
-    x.refresh();
-    x.each([&](int lane) { phase_kin_ankle<true>(c, L, x.reg(lane), q, lane); });
-    /* contacts in surface-major, sphere-minor order (ballot ranks follow lane order), at most MAXC kept:
-     * pass 0 = ground (13 lanes), pass 1 = all lateral half-spaces (13 lanes each), pass 2 = world boxes, then the item
-     * cubes near the robot (up to four cubes per pass, 13 lanes each), then the capsule pairs of different legs */
-    int nC = 0, nS = 0;
-#ifdef HRL_WGTIME
-    int n_cube_passes = 0;
-#endif
-    /* Broad phase (wave-uniform): every contact sphere lies within 1.25 m of the torso centre (hip 0.283 + aux 0.283 +
-     * foot 0.566 + radius 0.08 + contact_dist), so a lateral surface farther than that from the torso cannot produce a
-     * contact and its pass is skipped.  Exactly the same contact list as testing every pair. */
-    const float reach = 0.2f * 1.41421356f + c.L1 + c.L2 + c.r_caps + c.cdist + 0.02f;
-    /* no short-circuit operators in these wave-uniform tests: `a && b` on LDS operands compiles to one load -> wait -> branch per
-     * term, a chain of dependent round trips (8 of them in the joint-range test below cost 0.35 us per substep) */
-    bool near_plane = false, near_box = false;
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-        near_plane = near_plane | ((f < c.n_planes) & ((c.plane_n[f][0] * q[0] + c.plane_n[f][1] * q[1] + c.plane_n[f][2] * q[2]) - c.plane_d[f] < reach));
-    if (c.n_boxes > 0) {
-        float d2 = 0.f;
-        for (int k = 0; k < 3; ++k) { const float cp = clampf(q[k], c.box_lo[k], c.box_hi[k]); d2 += (q[k] - cp) * (q[k] - cp); }
-        near_box = d2 < reach * reach;
-    }
-    auto keep = [&](int base, bool up = false, bool on_box = false) {
-        return [&L, base, up, on_box](int, int rank, const Hit &h) { store_contact(L, base + rank, h, up, on_box); };
-    };
-    bool any_box = false; /* a pass against the box / a cube kept a contact: only then is there anything for second_support to look at */
-    for (int pass = 0; pass < 3; ++pass) {
-        const int nsurf = pass == 0 ? 1 : (pass == 1 ? c.n_planes : c.n_boxes);
-        if (nsurf == 0) continue;
-        if ((pass == 1 && !x.uniform(near_plane)) || (pass == 2 && !x.uniform(near_box))) continue;
-        const int f0 = pass == 0 ? 0 : (pass == 1 ? 1 : 1 + c.n_planes);
-        int cnt = x.each_compact(
-            [&](int lane) {
-                const int fi = lane / 13, sph = lane - 13 * fi;
-                return sphere_vs_surface(c, L, q, fi < nsurf ? sph : -1, f0 + fi, -1);
-            },
-            keep(nC, pass == 0, pass == 2),
-            [&](int lane, const Hit &h) { if (pass == 0 && lane < 16) L.gtouch[lane] = h.ok ? 1 : 0; });
-        nC += cnt;
-        if (nC > cap) nC = cap;
-        any_box = any_box | ((pass == 2) & (cnt > 0));
-    }
-    if (items_on) { /* food / poison cubes: lane = item decides whether its cube is within reach of any sphere (the cube's
-                       half extent more than the planes' bound, per axis), then the near cubes are tested four at a time */
-        const float R = reach + ITEM_HALF;
-        unsigned long long near = x.each_ballot([&](int lane) { /* lane = item (at most 64 of them) */
-            return (lane < c.n_food + c.n_poison) & (fabsf(q[0] - L.items[2 * lane]) < R) & (fabsf(q[1] - L.items[2 * lane + 1]) < R);
-        });
-        while (near) {
-#ifdef HRL_WGTIME
-            ++n_cube_passes;
-#endif
-            int it[4], n_it = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                it[k] = -1;
-                if (near) { it[k] = (int)__builtin_ctzll(near); near &= near - 1; ++n_it; }
-            }
-            const unsigned long long maybe = x.each_ballot([&](int lane) { /* see ant_contacts_group */
-                const int slot = lane / 13, sph = lane - 13 * slot;
-                const int item = slot == 0 ? it[0] : (slot == 1 ? it[1] : (slot == 2 ? it[2] : (slot == 3 ? it[3] : -1)));
-                return shape_near_item(c, L, q, sph, item);
-            });
-            if (!maybe) continue;
-            int cnt = x.each_compact(
-                [&](int lane) {
-                    const int slot = lane / 13, sph = lane - 13 * slot;
-                    const int item = slot == 0 ? it[0] : (slot == 1 ? it[1] : (slot == 2 ? it[2] : (slot == 3 ? it[3] : -1)));
-                    return sphere_vs_surface(c, L, q, item >= 0 ? sph : -1, 0, item);
-                },
-                keep(nC, false, true), [&](int, const Hit &) {});
-            nC += cnt;
-            if (nC > cap) nC = cap;
-            any_box = any_box | (cnt > 0);
-        }
-    }
-#ifndef HRL_NO_SECOND /* (A/B builds of tools/variants.py define it) */
-    if (x.uniform(any_box) && x.each_ballot([&](int lane) { int kf; return (lane < nC) & second_worth_a_look(c, L, lane < MAXC ? lane : 0, &kf); })) {
-        /* second support points of the capsules that lie flat on a face of the box / a cube: one pass over the kept contacts, lane = contact */
-        int cnt = x.each_compact([&](int lane) { return second_support(c, L, q, lane < nC ? lane : -1); }, keep(nC, false, true), [&](int, const Hit &) {});
-        nC += cnt;
-        if (nC > cap) nC = cap;
-    }
-#endif
-    if (c.self_collision) { /* Seen from above in the torso frame, leg l is the jointless capsule O -> hip point followed by the aux
-        and foot capsules, which both lie in the vertical plane through the hip point at 45 + 90 l degrees + hip angle: with
-        |ankle angle| <= 2 rad the foot folds back by at most 0.566 cos(2) = 0.24 m < the aux length, so everything past the
-        hip point projects onto the ray from it.  With every |hip angle| <= 0.75 rad those rays keep >= 0.2 m from the
-        coordinate axes (hence from the other legs' jointless capsules) and >= 0.4 m from one another, so no two capsule
-        axes of different legs come within 2 r + contact_dist < 0.2 m: the pair test is skipped -- the same contact list
-        as testing all 48 pairs (the joints' own limits are +-0.698 and +-1.745 rad). */
-        const bool thin = (c.r_caps + c.r_caps) + c.cdist < 0.2f;
-        const bool spread = x.each_ballot([&](int lane) { /* lane = joint: outside the safe range? */
-            return (lane < NJ) & !(thin & (fabsf(q[7 + (lane & 7)]) <= ((lane & 1) ? 2.0f : 0.75f)));
-        }) == 0;
-        if (!x.uniform(spread)) {
-            int cnt = x.each_compact([&](int lane) { return capsule_pair(c, L, lane < 48 ? lane : -1); }, keep(nC), [&](int, const Hit &) {});
-            nS = nC + cnt > cap ? cap - nC : cnt; /* self contacts among the kept ones: their rows take the two-body path */
-            nC += nS;
-        }
-    }
-    x.stamp(5);
-    x.each([&](int lane) {
-        if (lane == 0) {
-            L.nC = nC; L.nS = nS;
-#ifdef HRL_WGTIME
-            L.dbg_rows += (3 * nC) | (n_cube_passes << 16) | ((nS > 0 ? 1 : 0) << 24);
-#endif
-        }
-    });
-}
-
-/* Limit rows of ONE env's pose into its record (L.nL): like ant_contacts a function of the pose alone, run by whichever wave has
- * the time. */
-template <class X>
-HRL_DEV void ant_limits(X &x, const DevCfg &c, WaveLds &L, int qi) {
-    const float *q = L.q[qi];
-    x.refresh();
-    /* joint limits (lane = joint) */
-    int nL = x.each_compact(
-        [&](int lane) {
-            LimitHit r; r.ok = false; r.sgn = 0.f; r.dist = 0.f;
-            if (lane < NJ) {
-                float dlo = q[7 + lane] - L.jlim[0][lane], dhi = L.jlim[1][lane] - q[7 + lane];
-                if (dlo < c.lmargin) { r.ok = true; r.sgn = 1.f; r.dist = dlo; }
-                else if (dhi < c.lmargin) { r.ok = true; r.sgn = -1.f; r.dist = dhi; }
-            }
-            return r;
-        },
-        [&](int lane, int rank, const LimitHit &r) { L.ljoint[rank] = lane; L.lsign[rank] = r.sgn; L.ldist[rank] = r.dist; },
-        [&](int, const LimitHit &) {});
-    x.stamp(6);
-    x.each([&](int lane) {
-        if (lane == 0) {
-            L.nL = nL;
-#ifdef HRL_WGTIME
-            L.dbg_rows += nL;
-#endif
-        }
-    });
-}
-
 /* Contacts of ALL FOUR envs of a group by ONE wave, 16 lanes per env (lane >> 4 = env of the group, lane & 15 = sphere / item / joint):
  * the passes every substep runs -- leg points, the ground pass (13 spheres), the near-cube ballot and one cube per env and pass -- are
  * one instruction stream for the four envs instead of four streams (the group's vector-instruction count, which is what four workgroups per
  * CU contend for, falls by the contact phase of three envs); the passes that only envs near a wall / the maze box / with legs out of their
- * safe range need run env by env with all 64 lanes, as in ant_contacts.  Per env the candidate order is unchanged: ground, walls, box,
- * cubes in slot order -- each sphere-minor -- then the capsule pairs.  Results per record: the contact list, nC, nS, gtouch. */
+ * safe range need run env by env with all 64 lanes.  Per env the candidate order: ground, walls, box, cubes in slot order -- each
+ * sphere-minor (ballot ranks follow lane order) -- then the capsule pairs, at most c.max_contacts kept.  Results per record: the contact
+ * list, nC, nS, gtouch.  Like the limit rows this is a function of the pose alone (the leg points come from a POS_ONLY kinematics pass of
+ * its own), so it runs on wave 1 WHILE the leader works through the group block.
+ * No short-circuit operators in the wave-uniform tests: `a && b` on LDS operands compiles to one load -> wait -> branch per term, a chain
+ * of dependent round trips (8 of them in the joint-range test cost 0.35 us per substep). */
 template <class X>
 HRL_DEV void ant_contacts_group(X &x, const DevCfg &c, int qi, bool items_on) {
     x.refresh();
     const int cap = c.max_contacts;
     bool any_box = false; /* a pass against the maze box / a cube ran (rare): only then does second_support have anything to look at */
     x.each([&](int lane) { WaveLds &L = x.lds(lane >> 4); phase_kin_ankle<true>(c, L, x.reg(lane), L.q[qi], (lane & 15) << 2); });
+    /* Broad phase (wave-uniform): every contact sphere lies within 1.25 m of the torso centre (hip 0.283 + aux 0.283 +
+     * foot 0.566 + radius 0.08 + contact_dist), so a lateral surface farther than that from the torso cannot produce a
+     * contact and its pass is skipped.  Exactly the same contact list as testing every pair. */
     const float reach = 0.2f * 1.41421356f + c.L1 + c.L2 + c.r_caps + c.cdist + 0.02f;
     /* ground pass of the four envs; its count starts the env's list */
     x.each_compact16(
@@ -1545,7 +1384,8 @@ HRL_DEV void ant_contacts_group(X &x, const DevCfg &c, int qi, bool items_on) {
             x.each([&](int lane) { if (lane == 0) L.nC = nC; });
         }
     }
-    if (items_on) { /* lane = (env, item): cubes within reach of any sphere of their env's ant; then one near cube per env and pass.
+    if (items_on) { /* lane = (env, item): cubes within reach of any sphere of their env's ant (the cube's half extent more than the
+                       planes' bound, per axis); then one near cube per env and pass.
                        More than 16 items: slice after slice of 16 (one trip for the default configs), which keeps the slot order */
         const float R = reach + ITEM_HALF;
         const int n_items = c.n_food + c.n_poison;
@@ -1588,7 +1428,8 @@ HRL_DEV void ant_contacts_group(X &x, const DevCfg &c, int qi, bool items_on) {
         }
     }
 #ifndef HRL_NO_SECOND
-    if (x.uniform(any_box)) { /* second support points (see ant_contacts): lane = (env, kept contact), the four envs at once */
+    if (x.uniform(any_box)) { /* second support points of the capsules that lie flat on a face of the box / a cube: lane = (env, kept
+                                 contact), the four envs at once */
         const unsigned long long any = x.each_ballot([&](int lane) {
             const WaveLds &L = x.lds(lane >> 4);
             const int i = lane & 15;
@@ -1606,7 +1447,14 @@ HRL_DEV void ant_contacts_group(X &x, const DevCfg &c, int qi, bool items_on) {
         }
     }
 #endif
-    if (c.self_collision) { /* the envs with a joint outside the range in which no two legs can meet (see ant_contacts), one after the other */
+    if (c.self_collision) { /* Seen from above in the torso frame, leg l is the jointless capsule O -> hip point followed by the aux
+        and foot capsules, which both lie in the vertical plane through the hip point at 45 + 90 l degrees + hip angle: with
+        |ankle angle| <= 2 rad the foot folds back by at most 0.566 cos(2) = 0.24 m < the aux length, so everything past the
+        hip point projects onto the ray from it.  With every |hip angle| <= 0.75 rad those rays keep >= 0.2 m from the
+        coordinate axes (hence from the other legs' jointless capsules) and >= 0.4 m from one another, so no two capsule
+        axes of different legs come within 2 r + contact_dist < 0.2 m: the pair test is skipped -- the same contact list
+        as testing all 48 pairs (the joints' own limits are +-0.698 and +-1.745 rad).  The envs with a joint outside that
+        range run the pair test, one after the other. */
         const bool thin = (c.r_caps + c.r_caps) + c.cdist < 0.2f;
         const unsigned long long unsafe = x.each_ballot([&](int lane) { /* lane = (env, joint) */
             const float *q = x.lds(lane >> 4).q[qi];
@@ -1630,7 +1478,8 @@ HRL_DEV void ant_contacts_group(X &x, const DevCfg &c, int qi, bool items_on) {
 #endif
 }
 
-/* Limit rows of all four envs of a group by one wave: lane = (env, joint). */
+/* Limit rows of all four envs of a group by one wave, lane = (env, joint): like the contacts a function of the pose alone, run on
+ * wave 2 while the leader works through the group block. */
 template <class X>
 HRL_DEV void ant_limits_group(X &x, const DevCfg &c, int qi) {
     x.refresh();
@@ -1661,7 +1510,7 @@ HRL_DEV void ant_limits_group(X &x, const DevCfg &c, int qi) {
 }
 
 /* ENV block of a substep, on the env's own wave: on entry L.q[qi] / L.u / L.ustar, the articulated-body quantities of the group
- * block and the lists of ant_contacts are in the env's record; rows, sweeps, velocity reconstruction and clamp, then the
+ * block and the lists of ant_contacts_group are in the env's record; rows, sweeps, velocity reconstruction and clamp, then the
  * positions are integrated into L.q[qi ^ 1]. */
 template <class X>
 HRL_DEV int ant_env_block(X &x, const DevCfg &c, int qi) { /* returns the substep's solver rows (wave-uniform) */
@@ -1696,14 +1545,10 @@ HRL_DEV int ant_env_block(X &x, const DevCfg &c, int qi) { /* returns the subste
 
 /* Who finds the contacts and limit rows while the leader (wave 0) runs the group block (7.5 k cycles): wave 1 the contacts of all four
  * envs, lane-packed (ant_contacts_group), wave 2 their limit rows (ant_limits_group); wave 3 waits at the barrier.  Records of a ragged
- * last group that hold no env are computed along (their results are never used).  A group of one does everything itself, in order. */
+ * last group that hold no env are computed along (their results are never used). */
 template <class X>
 HRL_DEV void ant_contact_duty(X &x, const DevCfg &c, int qi, bool items_on) {
     const int w = x.wave_index();
-    if (x.group_size() == 1) {
-        if (x.uniform(x.lds().on)) { ant_contacts(x, c, x.lds(), qi, items_on); ant_limits(x, c, x.lds(), qi); }
-        return;
-    }
     if (w == 1) ant_contacts_group(x, c, qi, items_on);
     if (w == 2) ant_limits_group(x, c, qi);
 }

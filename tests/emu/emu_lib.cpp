@@ -17,9 +17,10 @@
 
 using namespace hrl;
 
-/* A workgroup of G env-waves: their LDS records and the workgroup barrier.  G = 1: the one-wave-per-env form.  G = 4: four
- * host threads run the four waves of a group concurrently, exactly as the kernel's workgroup does (step_core.h,
- * ant_group_block): the leader wave executes the group block on all four records while the others wait at the barrier. */
+/* A workgroup of G env-waves: their LDS records and the workgroup barrier.  G = 1: one wave per env (the point bot's step, reset,
+ * observe, goals).  G = 4 (the ant kinds' step): four host threads run the four waves of a group concurrently, exactly as the kernel's
+ * workgroup does (step_core.h, ant_group_block): the leader wave executes the group block on all four records while the others wait at
+ * the barrier. */
 struct CpuGroup {
     int G;
     WaveLds L[4];
@@ -35,13 +36,12 @@ struct CpuExec {
     bool reverse = false;
     CpuExec(CpuGroup &g, int w) : grp(g), wave(w) { memset(regs, 0, sizeof(regs)); }
     WaveLds &lds() { return grp.L[grp.G == 1 ? 0 : wave]; }
-    WaveLds &lds(int k) { return grp.L[grp.G == 1 ? 0 : k]; }
+    WaveLds &lds(int k) { return grp.L[k]; } /* record k of the group (G = 4 only) */
     void group_sync() { if (grp.G > 1) pthread_barrier_wait(&grp.bar); }
-    template <class F> void leader(F f) { if (grp.G == 1 || wave == 0) each(f); }
+    template <class F> void leader(F f) { if (wave == 0) each(f); }
     LaneRegs &reg(int lane) { return regs[lane]; }
     int uniform(int v) { return v; }
     int wave_index() const { return wave; }
-    int group_size() const { return grp.G; }
     void refresh() {}
     int slot() const { return 0; } /* scheduling hints of the device executor: no effect on results */
     void priority(int) const {}
@@ -124,12 +124,12 @@ int emu_observe(const hrl_config *cfg, const hrl_buffers *b, const uint8_t *mask
     for (int e = 0; e < cfg->num_envs; ++e) { CpuGroup g(1); CpuExec x(g, 0); x.reverse = reverse != 0; observe_dispatch(x, d, c, e); }
     return HRL_OK;
 }
-/* group = envs per workgroup: 4 = the product's launch for the ant kinds (four host threads per group), 1 = one wave per env */
-int emu_step_group(const hrl_config *cfg, const hrl_buffers *b, int reverse, int group) {
-    if (!validate(cfg).empty() || (group != 1 && group != 4)) return HRL_ERR_BAD_ARG;
+/* the library's launch: one wave per env for the point bot, groups of four (four host threads per group) for the ant kinds */
+int emu_step(const hrl_config *cfg, const hrl_buffers *b, int reverse) {
+    if (!validate(cfg).empty()) return HRL_ERR_BAD_ARG;
     DevCfg c; build_devcfg(*cfg, c);
     DevBufs d = to_dev(b, nullptr);
-    if (group == 1 || cfg->env_kind == HRL_POINT_GATHER) {
+    if (cfg->env_kind == HRL_POINT_GATHER) {
         for (int e = 0; e < cfg->num_envs; ++e) { CpuGroup g(1); CpuExec x(g, 0); x.reverse = reverse != 0; step_dispatch(x, d, c, e); }
         return HRL_OK;
     }
@@ -145,7 +145,6 @@ int emu_step_group(const hrl_config *cfg, const hrl_buffers *b, int reverse, int
     for (auto *g : groups) delete g;
     return HRL_OK;
 }
-int emu_step(const hrl_config *cfg, const hrl_buffers *b, int reverse) { return emu_step_group(cfg, b, reverse, 4); }
 int emu_set_goals(const hrl_config *cfg, const hrl_buffers *b, const float *goals_xy, int n_goals, const uint8_t *mask, int reverse) {
     if (!validate(cfg).empty() || cfg->env_kind != HRL_ANT_FLAGRUN || !cfg->flag_manual_goals || n_goals < 1 || n_goals > cfg->flag_goal_capacity) return HRL_ERR_BAD_ARG;
     DevCfg c; build_devcfg(*cfg, c);

@@ -786,14 +786,13 @@ def _item_boxes(o, i):
     return {(16 + k if k < 48 else 64 + k): (np.r_[it[k] - 0.125, -0.025], np.r_[it[k] + 0.125, 0.225]) for k in range(ni)}
 
 
-@pytest.mark.parametrize('group', [0, 1])
-def test_capsule_mid_sections_against_cubes_and_the_maze_box(group):
+def test_capsule_mid_sections_against_cubes_and_the_maze_box():
     """assets/ant.xml:16-55 capsules against assets/food.xml:12 cubes and the assets/box.xml:12 maze box: ants let down onto cubes with the
     MIDDLE of their feet (contact pickup, ant_gather_env.py:113-116: the touch is paid) and feet laid across the vertical edges of the maze
-    box -- contacts no end-point sphere sees; wave phases == oracle bit for bit, both launch shapes."""
+    box -- contacts no end-point sphere sees; wave phases == oracle bit for bit."""
     import capsule_cases as cc
     n = 32
-    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=4, auto_reset=1, robot_coll_dist=0.0, model_step_group=group)
+    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=4, auto_reset=1, robot_coll_dist=0.0)
     o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
     o.reset(); e.reset()
     rng = np.random.RandomState(8)
@@ -809,7 +808,7 @@ def test_capsule_mid_sections_against_cubes_and_the_maze_box(group):
                 assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (t, k, name)
             paid += int((o.info[:, 0] != 0).sum())
     assert mid >= 20 and paid >= 60, (mid, paid)
-    cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=4, auto_reset=1, model_step_group=group)
+    cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=4, auto_reset=1)
     o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
     o.reset(); e.reset()
     box = {8: (np.array([-5., -2, 0]), np.array([1., 2, 2]))}
@@ -924,16 +923,15 @@ def test_straggler_threshold_follows_the_model():
     assert np.percentile(rows, 95) <= 20.0 and np.percentile(rows, 90) >= 19.0 and (rows > 20).mean() < 0.02, np.percentile(rows, [50, 90, 95, 99])
 
 
-@pytest.mark.parametrize('group', [0, 1])
-def test_second_support_points_of_capsules_lying_flat_on_a_box_face(group):
+def test_second_support_points_of_capsules_lying_flat_on_a_box_face():
     """A capsule that rests flat on a face of the maze box (assets/box.xml:12) or on the top of an item cube (assets/food.xml:12) gets a SECOND support
     point (Bullet keeps a manifold there; with one point the capsule rocks): feet hanging alongside the box's vertical faces, legs stretched out level
-    over cubes -- states full of such contacts, counted; wave phases == oracle bit for bit in both launch shapes, the contact cap included."""
+    over cubes -- states full of such contacts, counted; wave phases == oracle bit for bit, the contact cap included."""
     import capsule_cases as cc
     n = 32
     rng = np.random.RandomState(12)
     for cap in (12, 5):
-        cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=4, auto_reset=1, model_step_group=group, model_max_contacts=cap)
+        cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=4, auto_reset=1, model_max_contacts=cap)
         o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
         o.reset(); e.reset()
         seconds = 0
@@ -947,7 +945,7 @@ def test_second_support_points_of_capsules_lying_flat_on_a_box_face(group):
                 for name in ('state', 'aux', 'obs', 'rew', 'done', 'info', 'solver_rows'):
                     assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (cap, t, k, name)
         assert seconds >= (60 if cap == 12 else 10), (cap, seconds)
-    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=4, auto_reset=1, robot_coll_dist=0.0, model_step_group=group)
+    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=4, auto_reset=1, robot_coll_dist=0.0)
     o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
     o.reset(); e.reset()
     seconds = paid = 0

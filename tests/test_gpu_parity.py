@@ -330,8 +330,8 @@ def test_env_counts_that_do_not_fill_the_last_group(n):
 
 @pytest.mark.parametrize('kind', [K.HRL_ANT_GATHER, K.HRL_ANT_MAZE])
 def test_one_wave_per_env_launch_matches_too(kind):
-    """hrl_model.step_group = 1 (the measurement reference: one 64-thread workgroup per env, the same phases in order on the env's own
-    wave) is the same arithmetic: bit-exact against the oracle like the grouped launch."""
+    """hrl_model.step_group = 1 (kept for ABI v7 configs; it launches the same four-wave group as 0) is accepted and bit-exact against
+    the oracle like the default."""
     n = 96
     g, o = make(kind, n, seed=13, max_episode_steps=23, model_step_group=1)
     g.reset(); o.reset()
@@ -541,7 +541,7 @@ def test_capsule_mid_sections_against_cubes_and_the_maze_box_on_device():
 def test_second_support_points_on_device():
     """A capsule that rests flat on a face of the maze box or on the top of an item cube gets a SECOND support point (Bullet keeps a manifold there):
     feet hanging alongside the box's vertical faces, legs stretched out level over cubes (tests/capsule_cases.py) -- states full of such contacts,
-    counted; device == oracle bit for bit, the default group launch and the one-wave-per-env shape, a tight contact cap included."""
+    counted; device == oracle bit for bit, with hrl_model.step_group 0 and 1 (both the four-wave group), a tight contact cap included."""
     import capsule_cases as cc
     n = 256
     rng = np.random.RandomState(12)

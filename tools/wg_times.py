@@ -69,19 +69,19 @@ def main():
                       ('wave index in its workgroup', np.tile(np.arange(n) & 3, 20))):
         print(f'  mean life by {name}: ' + ', '.join(f'{int(k)}: {life[key == k].mean():.0f} (n={int((key == k).sum())})' for k in np.unique(key)))
     dbg = v[:, 3] >> 8
-    rows, cubes, selfs = (dbg & 0xffff).astype(float), ((dbg >> 16) & 0xff).astype(float), ((dbg >> 24) & 0xff).astype(float)
+    rows, selfs = (dbg & 0xffff).astype(float), ((dbg >> 24) & 0xff).astype(float)
     if rows.max() > 0:
         # a workgroup lives as long as its slowest env: group quantities = max over the four envs
         g = lambda a: a.reshape(-1, 4).max(axis=1)
-        gl, gr, gc, gs = g(life), g(rows), g(cubes), g(selfs)
+        gl, gr, gs = g(life), g(rows), g(selfs)
         print(f'  per step and env: solver rows summed over the substeps mean {rows.mean():.1f} (p10 {np.percentile(rows, 10):.0f}, p90 {np.percentile(rows, 90):.0f}, '
-              f'max {rows.max():.0f}); cube passes {cubes.mean():.2f}; substeps with self contacts {selfs.mean():.3f}')
-        print(f'  correlation of a workgroup\'s life with (max over its envs of) rows {np.corrcoef(gl, gr)[0, 1]:.3f}, cube passes {np.corrcoef(gl, gc)[0, 1]:.3f}, '
+              f'max {rows.max():.0f}); substeps with self contacts {selfs.mean():.3f}')
+        print(f'  correlation of a workgroup\'s life with (max over its envs of) rows {np.corrcoef(gl, gr)[0, 1]:.3f}, '
               f'self substeps {np.corrcoef(gl, gs)[0, 1]:.3f}')
-        A = np.stack([np.ones_like(gr), gr, gc, gs], axis=1)
+        A = np.stack([np.ones_like(gr), gr, gs], axis=1)
         coef, *_ = np.linalg.lstsq(A, gl, rcond=None)
         res = gl - A @ coef
-        print(f'  least squares: life = {coef[0]:.0f} + {coef[1]:.1f} * rows + {coef[2]:.0f} * cube passes + {coef[3]:.0f} * self substeps; residual sd {res.std():.0f} of sd {gl.std():.0f}')
+        print(f'  least squares: life = {coef[0]:.0f} + {coef[1]:.1f} * rows + {coef[2]:.0f} * self substeps; residual sd {res.std():.0f} of sd {gl.std():.0f}')
     widx, simd = np.tile(np.arange(n) & 3, 20), (hw >> 4) & 3
     print('  waves by (index in workgroup, SIMD_ID): ' + ' | '.join(' '.join(str(int(((widx == i) & (simd == j)).sum())) for j in range(4)) for i in range(4)))
     if rows.max() > 0:
