@@ -15,6 +15,8 @@ HRL_MAX_TARGETS = 64
 HRL_MAX_GOALS = 61
 HRL_FLAG_GOAL_OFF, HRL_FLAG_START_OFF, HRL_FLAG_SQDIST_OFF, HRL_FLAG_PENDING_OFF = 0, 2, 4, 6  # flagrun items record
 HRL_GOAL_STRIDE = 4
+HRL_CONTACT_MAX, HRL_CONTACT_WIDTH, HRL_CONTACTS_HEADER, HRL_CONTACTS_STRIDE = 12, 20, 16, 256  # the optional step output `contacts`
+HRL_SURF_BOX, HRL_SURF_ITEM, HRL_SURF_SELF = 8, 16, 64  # surface codes of a contact
 HRL_OK, HRL_ERR_BAD_ARG, HRL_ERR_HIP, HRL_ERR_NO_DEVICE = 0, 1, 2, 3
 
 
@@ -70,10 +72,28 @@ class hrl_buffers(C.Structure):
         if args:
             raise TypeError('hrl_buffers takes keywords only (its first field is struct_size)')
         super().__init__(**kw)
-        self.struct_size = C.sizeof(hrl_buffers)
+        self.struct_size = C.sizeof(type(self))
 
 
-def make_buffers(state, items, aux, actions, obs, reward, done, info, final_obs=None, truncated=None, goal=None, solver_rows=None):
-    """An initialised buffer record from addresses (ints / c_void_p / None), in the order of include/hrl_envs.h."""
-    return hrl_buffers(state=state, items=items, aux=aux, actions=actions, obs=obs, reward=reward, done=done, info=info,
-                       final_obs=final_obs, truncated=truncated, goal=goal, solver_rows=solver_rows)
+class hrl_buffers_ext(hrl_buffers):
+    """hrl_buffers followed by the optional outputs added after the v7 record was cut (include/hrl_envs.h: hrl_buffers_ext); goes wherever an
+    hrl_buffers goes, its struct_size says that there is more."""
+    _fields_ = [('contacts', C.c_void_p)]
+
+    @classmethod
+    def of(cls, b):
+        """`b` (an hrl_buffers) as the longer record, the outputs behind it off."""
+        if isinstance(b, cls):
+            return b
+        e = cls()
+        for name, _ in hrl_buffers._fields_[1:]:
+            setattr(e, name, getattr(b, name))
+        return e
+
+
+def make_buffers(state, items, aux, actions, obs, reward, done, info, final_obs=None, truncated=None, goal=None, solver_rows=None, contacts=None):
+    """An initialised buffer record from addresses (ints / c_void_p / None), in the order of include/hrl_envs.h; with `contacts` the longer
+    hrl_buffers_ext."""
+    kw = dict(state=state, items=items, aux=aux, actions=actions, obs=obs, reward=reward, done=done, info=info,
+              final_obs=final_obs, truncated=truncated, goal=goal, solver_rows=solver_rows)
+    return hrl_buffers(**kw) if contacts is None else hrl_buffers_ext(contacts=contacts, **kw)

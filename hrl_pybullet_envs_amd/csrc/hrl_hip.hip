@@ -287,6 +287,8 @@ DevBufs to_dev(const hrl_buffers *b, const uint8_t *mask) {
     d.state = b->state; d.items = b->items; d.aux = b->aux; d.actions = b->actions; d.obs = b->obs;
     d.reward = b->reward; d.done = b->done; d.info = b->info; d.mask = mask;
     d.final_obs = HRL_OPT(b, final_obs); d.truncated = HRL_OPT(b, truncated); d.goal = HRL_OPT(b, goal); d.rows = HRL_OPT(b, solver_rows);
+    /* the outputs behind the v7 record (hrl_buffers_ext): there when the caller's struct_size says so */
+    d.contacts = b->struct_size >= offsetof(hrl_buffers_ext, contacts) + sizeof(float *) ? reinterpret_cast<const hrl_buffers_ext *>(b)->contacts : nullptr;
     d.stamps = g_stamps;
     return d;
 }
@@ -307,7 +309,7 @@ namespace {
  * is a thread-local read: ~20 ns, tools/host_overhead.py). */
 int check_call(const hrl_handle *h, const hrl_buffers *b, const char *who) {
     if (!h || !b) return fail(HRL_ERR_BAD_ARG, std::string(who) + ": null handle or buffer record");
-    if (b->struct_size < HRL_BUFFERS_SIZE_V7_BASE || b->struct_size > sizeof(hrl_buffers) || b->struct_size % sizeof(void *) != 0)
+    if (b->struct_size < HRL_BUFFERS_SIZE_V7_BASE || b->struct_size > sizeof(hrl_buffers_ext) || b->struct_size % sizeof(void *) != 0)
         return fail(HRL_ERR_BAD_ARG, std::string(who) + ": hrl_buffers.struct_size = " + std::to_string((unsigned long long)b->struct_size) +
                                          " is not the size of a known layout: initialise the record with hrl_buffers_init() (include/hrl_envs.h)");
     int cur = -1;

@@ -111,6 +111,10 @@ struct DevBufs {
     int32_t *rows;      /* optional, diagnostic: += solver rows of the step (limits + 3 x contacts over its substeps) */
     const uint8_t *mask;
     unsigned long long *stamps; /* diagnostic builds only (tools/stamp_profile.py): per-phase cycle sums */
+    float *contacts = nullptr; /* optional: the contact report of the step's last collision pass and solve, [N][HRL_CONTACTS_STRIDE] (include/hrl_envs.h).
+                                  Default-initialised: a host that fills the record field by field and does not know this one leaves it off.  LAST: the
+                                  kernel-argument offsets of the other fields stay what they were (behind `rows` the gather launch was 0.4 us longer with the
+                                  report off, profiles/EXPERIMENTS.md 10) */
 };
 
 /* Per-wave LDS record ("LDS-staged link/joint state"), 7.5 KB, 16-byte aligned (wide LDS accesses).  Three users with disjoint lifetimes share the first
@@ -2332,6 +2336,53 @@ HRL_DEV void set_goals_entry(X &x, const DevBufs &b, const DevCfg &c, int e, con
     store_env(x, b, c, e);
 }
 
+/* The optional contact report (hrl_buffers_ext::contacts, layout in include/hrl_envs.h): what the step's LAST substep left in the env's record --
+ * the kept contacts (cr, cdir, cdist_, csurf, clink, clink2, cmu), the limit rows (ljoint, lsign) and the solved impulses (lamf: limits, normals,
+ * friction pairs) -- as one 1 KiB record per env.  Lane l owns floats [4 l, 4 l + 4): lanes 0-3 the header, lanes 4 + 5 i .. 8 + 5 i contact i
+ * (position | distance, then the three frame rows each with its impulse, then the codes), so a lane reads one float[4]-shaped LDS row, selects
+ * its fourth component and the wave stores 64 x 16 bytes, contiguous.  Everything beyond the step's contacts is +0.0: the record is a pure
+ * function of the step.  q0 = the pose the last collision pass saw; n_contacts / nL wave-uniform.  KIND 3 (the point bot) has no limit rows
+ * and stores neither links nor a per-contact friction: 0, -1 and c.mu.  Reads LDS only: no register or LDS state of its own. */
+template <int KIND, class X>
+HRL_DEV void write_contacts(X &x, const DevCfg &c, float *rec, const float *q0, int n_contacts, int nL) {
+    const WaveLds &L = x.lds();
+    x.each([&](int lane) {
+        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+        const int nR = nL + 3 * n_contacts;
+        if (lane == 0) { v0 = (float)n_contacts; v1 = (float)nL; v2 = (float)nR; v3 = c.h; }
+        else if (lane < 3) { /* joints 4 (lane - 1) ..: lsign x lambda of the joint's limit row */
+            for (int k = 0; k < nL; ++k) {
+                const int j = (L.ljoint[k] & 7) - 4 * (lane - 1);
+                const float f = L.lsign[k] * L.lamf[k];
+                v0 = j == 0 ? f : v0; v1 = j == 1 ? f : v1; v2 = j == 2 ? f : v2; v3 = j == 3 ? f : v3;
+            }
+        } else if (lane == 3) {
+            int held = 0, neg = 0;
+            for (int k = 0; k < nL; ++k) { const int bit = 1 << (L.ljoint[k] & 7); held |= bit; neg |= L.lsign[k] < 0.f ? bit : 0; }
+            v0 = (float)held; v1 = (float)neg;
+        } else {
+            const int m = lane - 4, i = m / 5, w = m - 5 * i; /* i < 12 */
+            if (i < n_contacts) {
+                if (w == 0) { v0 = L.cr[i][0] + q0[0]; v1 = L.cr[i][1] + q0[1]; v2 = L.cr[i][2] + q0[2]; v3 = L.cdist_[i]; }
+                else if (w < 4) {
+                    const int d = w - 1;
+                    v0 = L.cdir[d][i][0]; v1 = L.cdir[d][i][1]; v2 = L.cdir[d][i][2];
+                    v3 = L.lamf[d == 0 ? nL + i : nL + n_contacts + 2 * i + (d - 1)];
+                } else {
+                    v0 = (float)L.csurf[i];
+                    v1 = KIND == 3 ? 0.f : (float)L.clink[i]; v2 = KIND == 3 ? -1.f : (float)L.clink2[i]; v3 = KIND == 3 ? c.mu : L.cmu[i];
+                }
+            }
+        }
+#ifdef HRL_EMU
+        float *o = rec + 4 * lane;
+        o[0] = v0; o[1] = v1; o[2] = v2; o[3] = v3;
+#else
+        reinterpret_cast<float4 *>(rec)[lane] = make_float4(v0, v1, v2, v3); /* one 16-byte vector store per lane: 1 KiB per wave, contiguous */
+#endif
+    });
+}
+
 /* hrl_step for one env (one wave; the waves of a workgroup form a group, see ant_group_block).  e >= n_envs: a wave of the
  * last group without an env of its own, which only takes part in the group's barriers. */
 template <int KIND, class X>
@@ -2415,6 +2466,8 @@ HRL_DEV void step_entry(X &x, const DevBufs &b, const DevCfg &c, int e) {
                    formed here, not kept in registers since the loads (the point kernel, at its register cap, spilled the id around the loop) */
     HRL_PIN_VGPR(eo);
     const long long env = c.env_id_offset + eo;
+    if (b.contacts) /* a kernel argument: a scalar branch; the report of the last substep, before the epilogue reuses LDS and before a reset */
+        write_contacts<KIND>(x, c, b.contacts + (size_t)eo * HRL_CONTACTS_STRIDE, L.q[qi ^ 1], n_contacts, KIND == 3 ? 0 : x.uniform(L.nL));
     x.each([&](int lane) { /* back to the packed record */
         if (lane < 15) L.st[lane] = L.q[qi][lane];
         if (lane >= 16 && lane < 30) {

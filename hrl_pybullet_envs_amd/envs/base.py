@@ -180,6 +180,23 @@ class BatchedGymEnv:
             return obs[0].astype(np.float64), float(rew[0]), d, out
         return env.step(a)
 
+    def record_contacts(self, on=True):
+        """From now on every step also writes the contact report: returns the [N, 256] tensor (BatchedEnv.record_contacts; `contacts.decode` names
+        its fields).  `on=False` switches it off again."""
+        return self._backend().record_contacts(on)
+
+    def get_contact_points(self, index=0):
+        """The contacts of env `index` in the last step's final collision pass, as a list of dicts (position, normal, distance, normal_force,
+        lateral_friction1/2 with their directions, kind 'ground' / 'wall' / 'box' / 'item' / 'self', item, link, link2): what
+        `p.getContactPoints(...)` answers in the reference after `stepSimulation()` (ant_gather_env.py:113-116).  The first call switches the
+        recording on (BatchedEnv.record_contacts): the steps taken from then on are reported, before it the list is empty -- call it once after
+        reset() when the first steps matter.  Forces in newtons (impulse of the last substep / its length)."""
+        from .. import contacts
+        env = self._backend()
+        if getattr(env, 'contacts', None) is None:
+            env.record_contacts()
+        return contacts.as_list(env.contacts, index)
+
     def close(self):
         if self._env is not None:
             self._env.close()

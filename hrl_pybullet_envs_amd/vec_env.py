@@ -124,6 +124,23 @@ class BatchedEnv:
             self._hbufs.solver_rows = p
         return self.solver_rows
 
+    def record_contacts(self, on=True):
+        """From now on every step writes `self.contacts` [N, HRL_CONTACTS_STRIDE] (float32): per env the contacts of the step's last collision
+        pass -- point, normal, distance, link, surface -- and their solved impulses, what `p.getContactPoints()` answers in the reference
+        (hrl_buffers_ext.contacts; contacts.decode() names the fields).  Written by the step's own launch, before an auto-reset; the tensor never
+        moves, so a captured graph keeps writing it.  step_host() leaves it on the device.  Not part of state_dict(): it is an output."""
+        self.contacts = torch.zeros(self.num_envs, K.HRL_CONTACTS_STRIDE, dtype=torch.float32, device=self.device) if on else None
+        p = self.contacts.data_ptr() if on else None
+        if on:   # the pointer lives in the longer record (hrl_buffers_ext); until it is asked for, the library is handed the plain v7 record
+            self._bufs, self._bufs_with_items = K.hrl_buffers_ext.of(self._bufs), K.hrl_buffers_ext.of(self._bufs_with_items)
+            self._bufs_ref = C.byref(self._bufs)
+            if self._host is not None:   # step_host()'s record too
+                self._hbufs = K.hrl_buffers_ext.of(self._hbufs)
+        for b in (self._bufs, self._bufs_with_items, self._hbufs if self._host is not None else None):
+            if isinstance(b, K.hrl_buffers_ext):
+                b.contacts = p
+        return self.contacts
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
@@ -194,6 +211,9 @@ class BatchedEnv:
                                          t['obs'].data_ptr(), t['rew'].data_ptr(), t['done'].data_ptr(), t['info'].data_ptr(),
                                          t['final_obs'].data_ptr(), t['trunc'].data_ptr(), t['goal'].data_ptr() if 'goal' in t else None)
             self._hbufs.solver_rows = self._bufs.solver_rows   # the diagnostic counter, when count_solver_rows() switched it on
+            if isinstance(self._bufs, K.hrl_buffers_ext):      # the contact report, when record_contacts() switched it on
+                self._hbufs = K.hrl_buffers_ext.of(self._hbufs)
+                self._hbufs.contacts = self._bufs.contacts
         h = self._host_np
         h['act'][...] = actions
         with torch.cuda.device(self.device):

@@ -63,6 +63,15 @@ extern "C" {
 #define HRL_FLAG_SQDIST_OFF 4
 #define HRL_FLAG_PENDING_OFF 6
 #define HRL_GOAL_STRIDE 4   /* optional flagrun output `goal`: current goal x, y | 1 if this step switched to it (info['target']) | steps since the goal changed */
+/* optional step output `contacts` (hrl_buffers_ext): one fixed record per env, the contacts of the step's last collision pass and their solved impulses */
+#define HRL_CONTACT_MAX 12      /* contacts per record = the most the solver keeps per substep (hrl_model.max_contacts <= 12) */
+#define HRL_CONTACT_WIDTH 20    /* floats per contact */
+#define HRL_CONTACTS_HEADER 16  /* floats before the first contact */
+#define HRL_CONTACTS_STRIDE 256 /* floats per env: 16 + 12 * 20 = 1 KiB */
+/* surface code of a contact (float +16 of a contact): 0 the ground, 1.. the lateral planes (walls) in the scene's order, then */
+#define HRL_SURF_BOX 8   /* HRL_SURF_BOX + b: world box b (the maze's one box: 8) */
+#define HRL_SURF_ITEM 16 /* HRL_SURF_ITEM + i: item cube i < 48 (food slots first, then poison); cubes 48..63: HRL_SURF_SELF + i */
+#define HRL_SURF_SELF 64 /* HRL_SURF_SELF + p, p < 48: capsule pair p of two legs (self contact; link2 >= 0 tells it from a cube >= 48) */
 
 /* status codes */
 #define HRL_OK 0
@@ -223,6 +232,34 @@ typedef struct hrl_buffers {
     int32_t *solver_rows; /* [N]                    in/out (step only, optional) */
 } hrl_buffers;
 #define HRL_BUFFERS_SIZE_V7_BASE ((uint64_t)(sizeof(uint64_t) + 8 * sizeof(void *))) /* through `info`: the least a v7 caller hands over */
+
+/* hrl_buffers followed by the optional outputs that came after ABI v7's record was cut: the v7 record itself keeps its size, a longer record carries
+ * more.  Pass `&x.base` wherever a `const hrl_buffers *` is taken, with `x.base.struct_size = sizeof x` (`hrl_buffers_ext x = {{sizeof x}};` zeroes the
+ * rest): the library reads what lies beyond hrl_buffers only within struct_size, so a caller that hands over a plain hrl_buffers has the outputs below off. */
+typedef struct hrl_buffers_ext {
+    hrl_buffers base;
+    /* Contact report: what `p.getContactPoints(...)` returns after stepSimulation() (ant_gather_env.py:113-116, gather_base.py:103-106, upstream's
+     * robot.feet_contact) -- which bodies touch what, where, and how hard.  hrl_step writes one record of HRL_CONTACTS_STRIDE floats per env, in the
+     * same launch: the step's LAST collision pass and solve (its last substep).  16-byte aligned (the record is stored as 64 16-byte vectors).
+     *   header   [0] n_contacts  [1] n_limit_rows  [2] n_rows = [1] + 3 [0]  [3] the substep h (model.timestep): force = impulse / [3]
+     *            [4..11] generalised impulse on joint j (hip_1, ankle_1, ..., ankle_4) from its limit row, signed (sign x lambda); 0 where the joint
+     *                    holds no row; all 0 for the point bot
+     *            [12] bit mask of the joints that hold a limit row  [13] of those whose row has sign -1  [14..15] 0
+     *   contact i < n_contacts, in the solver's contact order, at float HRL_CONTACTS_HEADER + HRL_CONTACT_WIDTH * i:
+     *            +0..2 world position (the point relative to the torso / body origin + that origin as the collision pass saw it: the pose at the
+     *                  start of the step's last substep)                                   +3  signed distance
+     *            +4..6 normal (towards the robot body; self contacts: towards the first body) +7  lambda normal
+     *            +8..10 tangent 1   +11 lambda t1     +12..14 tangent 2   +15 lambda t2
+     *            +16 surface code (HRL_SURF_*)  +17 link (level | leg << 2; 0 for the point bot)  +18 link2 (-1 unless a self contact)
+     *            +19 the contact's friction coefficient
+     * lambda are impulses of one substep (N s), the solver's own values.  Counts, masks and codes are stored as floats (<= 255: exact).  Contacts
+     * i >= n_contacts and the spare header floats are written as +0.0 in every step: a record is a pure function of the step, whole records
+     * compare bit for bit.  Written for every env in every hrl_step when the pointer is non-NULL, BEFORE an auto-reset (a finished env reports its
+     * terminal step); hrl_reset, hrl_observe, hrl_set_goals and hrl_next_target never touch it.  NULL (the default): nothing is computed or stored.
+     * Cost at 4096 envs per launch (profiles/EXPERIMENTS.md 10): written, +1.9 us on AntGather's 51.8 us, +1.7 us on AntMaze's 55.3 us, +0.7 us on the
+     * point bot's 50.1 us; NULL, one scalar branch. */
+    float *contacts;      /* [N][HRL_CONTACTS_STRIDE] out (step only, optional) */
+} hrl_buffers_ext;
 
 typedef struct hrl_handle hrl_handle;
 

@@ -1,0 +1,162 @@
+"""The step's optional contact report (hrl_buffers_ext.contacts, BatchedEnv.record_contacts) on the MI355X: the kernel's records against the
+lock-step host executor (whole records, bit for bit) and against the oracle directly, that switching it on changes nothing else, what a
+finished env reports, the host / hipGraph paths and the one-env classes.  Scenarios and references: tests/contacts_cases.py."""
+import numpy as np
+import pytest
+import torch
+
+import contacts_cases as cc
+
+pytestmark = pytest.mark.gpu
+
+
+def device_env(cfg, record=True):
+    from hrl_pybullet_envs_amd.vec_env import BatchedEnv
+    g = BatchedEnv(cfg, 'cuda:0')
+    g.reset()
+    if record:
+        g.record_contacts().fill_(float('nan'))  # every float must be written by the step
+    return g
+
+
+def push(g, s):
+    g.state.copy_(torch.tensor(s['state'])); g.items.copy_(torch.tensor(s['items'])); g.aux.copy_(torch.tensor(s['aux']))   # (copies: the trace is read-only)
+
+
+def device_records(tr, g=None):
+    g = g or device_env(tr.cfg)
+    rec = cc.run(tr, g, lambda env, a: env.step(torch.tensor(a).cuda()), fetch=lambda env: env.contacts.cpu().numpy(), push=push)
+    g.close()
+    return rec
+
+
+@pytest.mark.parametrize('name,n', [(name, None) for name in cc.NAMES] + [('items', 5), ('items', 1), ('point', 5), ('self', 5)])
+def test_device_records_equal_the_emulator_bit_for_bit(name, n):
+    """Identical inputs each step (state, items, aux, actions of the scenario's trace): the [N, 256] record array of the kernel == the host
+    executor's as uint32.  N = 5 and N = 1: a ragged last group of four whose spare records are parked, and a single record."""
+    tr = cc.trace(name, n)
+    dev, emu = device_records(tr), cc.emu_records(name, n)
+    assert not np.isnan(dev).any()
+    assert dev[:, :, 0].sum() > 0 or name == 'self'   # (five envs of the self scenario need not touch; the full one does)
+    for t in range(len(tr.steps)):
+        assert np.array_equal(cc.bits(dev[t]), cc.bits(emu[t])), (name, t, np.argwhere(cc.bits(dev[t]) != cc.bits(emu[t]))[:4])
+
+
+def test_device_records_equal_the_oracle_directly():
+    """Scenario (b) -- cubes, ground, limit rows, the contact cap -- without the emulator in between: counts, surface codes and every impulse
+    of the kernel's record == the oracle's replay of the step, bitwise."""
+    tr = cc.trace('items')
+    dev = device_records(tr)
+    for t, s in enumerate(tr.steps):
+        for i, rp in enumerate(s['replay']):
+            cc.check_against_oracle(dev[t, i], rp, (t, i))
+    assert any(rp['n_contacts'] == cc.MAXC for s in tr.steps for rp in s['replay'])
+
+
+@pytest.mark.parametrize('name', ['items', 'point'])
+def test_off_means_off(name):
+    """The same free-running rollout with and without record_contacts(): state, items, aux and every output identical bitwise."""
+    tr = cc.trace(name)
+    a_env, b_env = device_env(tr.cfg), device_env(tr.cfg, record=False)
+    for s in tr.steps:
+        a = torch.tensor(s['act']).cuda()
+        ra, rb = a_env.step(a), b_env.step(a)
+        for x, y in list(zip(ra[:3], rb[:3])) + [(a_env.state, b_env.state), (a_env.items, b_env.items), (a_env.info, b_env.info), (a_env.final_obs, b_env.final_obs)]:
+            assert np.array_equal(x.cpu().numpy().view(np.uint8), y.cpu().numpy().view(np.uint8))
+        assert torch.equal(a_env.aux, b_env.aux) and torch.equal(a_env.truncated, b_env.truncated)
+    assert getattr(b_env, 'contacts', None) is None and 'contacts' not in a_env.state_dict()
+    # switching it off again: the tensor is left alone from then on
+    last = a_env.contacts.clone()
+    a_env.record_contacts(False)
+    a_env.step(a)
+    torch.cuda.synchronize()
+    assert a_env.contacts is None and not torch.isnan(last).any()
+    a_env.close(); b_env.close()
+
+
+def test_a_finished_env_reports_its_terminal_step():
+    """max_episode_steps = 5 with auto-reset: in the step that sets `done` the record is the oracle's replay of THAT step (from the state
+    before it), not of the reset state the env holds afterwards."""
+    tr = cc.trace('random', max_episode_steps=5)
+    dev = device_records(tr)
+    ended = tells = 0
+    for t, s in enumerate(tr.steps):
+        for i, rp in enumerate(s['replay']):
+            cc.check_against_oracle(dev[t, i], rp, (t, i))
+            if s['done'][i]:
+                ended += 1
+                # what a record written AFTER the reset would hold: the same action applied to the state the env was reset to
+                late = cc.oracle_replay(tr.cfg, s['after'][i], s['items'][i], s['act'][i])
+                tells += (late['n_rows'], late['lam'].tobytes()) != (rp['n_rows'], rp['lam'].tobytes())
+    # the ants are still falling when the limit cuts in (they land around step 10): the records that tell the two apart are limit rows
+    assert ended >= tr.cfg.num_envs and tells >= ended // 2, (ended, tells)
+
+
+def test_step_host_and_a_graph_replay_write_the_same_record():
+    tr = cc.trace('items')
+    eager = device_records(tr)
+    # step_host(): actions from and outputs to pinned host memory, the report stays in HBM
+    g = device_env(tr.cfg)
+    host = cc.run(tr, g, lambda env, a: env.step_host(a), fetch=lambda env: env.contacts.cpu().numpy(), push=push)
+    g.close()
+    assert np.array_equal(cc.bits(host), cc.bits(eager))
+    # switched on AFTER the host record exists: step_host()'s record follows
+    g = device_env(tr.cfg, record=False)
+    g.step_host(tr.steps[0]['act'])
+    g.record_contacts()
+    push(g, tr.steps[12]); g.step_host(tr.steps[12]['act'])
+    assert np.array_equal(cc.bits(g.contacts.cpu().numpy()), cc.bits(eager[12]))
+    g.close()
+    # one captured step, replayed: the pointer is fixed, the replay writes the same tensor
+    g = device_env(tr.cfg)
+    static_a = torch.tensor(tr.steps[0]['act']).cuda()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):   # the warm-up launch torch asks for before a capture
+        g.step(static_a)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        g.step(static_a)
+    for t in (10, 11):
+        push(g, tr.steps[t]); static_a.copy_(torch.tensor(tr.steps[t]['act']))
+        g.contacts.fill_(float('nan'))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(cc.bits(g.contacts.cpu().numpy()), cc.bits(eager[t])), t
+    del graph
+    g.close()
+
+
+def test_single_env_get_contact_points():
+    """`AntGatherBulletEnv().get_contact_points()`: the first call switches the recording on (nothing recorded yet: an empty list); after 20
+    steps it names the ground contacts of the standing / tumbling ant, which carry its weight."""
+    import hrl_pybullet_envs_amd as H
+    from hrl_pybullet_envs_amd import contacts
+    env = H.AntGatherBulletEnv(seed=3)
+    env.reset()
+    assert env.get_contact_points() == []
+    rng = np.random.RandomState(0)
+    for _ in range(20):
+        env.step(rng.uniform(-1, 1, 8))
+    pts = env.get_contact_points()
+    ground = [p for p in pts if p['kind'] == 'ground']
+    assert ground and all(p['normal'] == (0.0, 0.0, 1.0) and p['link2'] == -1 and abs(p['position'][2] - 0.005 - p['distance']) < 1e-5 for p in ground)
+    assert sum(p['normal_force'] for p in ground) > 0
+    d = contacts.decode(env._backend().contacts, env._cfg)
+    assert int(d['n'][0]) == len(pts) and d['normal_force'].device.type == 'cuda'
+    lf = contacts.link_force(d)
+    up = sum(p['normal_force'] * p['normal'][2] + p['lateral_friction1'] * p['lateral_friction_dir1'][2] + p['lateral_friction2'] * p['lateral_friction_dir2'][2] for p in pts)
+    assert lf.shape == (1, 9, 3) and float(lf[0, :, 2].sum()) == pytest.approx(up, rel=1e-4)
+    env.close()
+    # the batched class: record_contacts() hands out the tensor every step rewrites
+    env = H.AntGatherBulletEnv(num_envs=8, seed=3)
+    env.reset()
+    raw = env.record_contacts()
+    for _ in range(14):
+        env.step(torch.from_numpy(rng.uniform(-1, 1, (8, 8)).astype(np.float32)).cuda())
+    d = contacts.decode(raw, env._cfg)
+    assert raw.shape == (8, 256) and int(d['n'].min()) > 0 and bool((d['kind'][d['valid']] == contacts.GROUND).all())
+    up = contacts.link_force(d)[:, :, 2].sum(1)   # ground contacts push up or, still closing within the contact distance, not at all
+    assert bool((up >= 0).all()) and int((up > 0).sum()) >= 4
+    env.close()

@@ -40,6 +40,7 @@ def main():
     envs = {}
     acts = torch.rand(64, n, act_dim, device='cuda') * 2 - 1
     libs['product+final'] = libs['product']  # the same library with the optional final_obs / truncated outputs of ABI v6 wired up
+    libs['product+contacts'] = libs['product']  # the same library writing the contact report (hrl_buffers.contacts: 1 KiB per env and step)
     for name, L in libs.items():
         h = C.c_void_p()
         assert L.hrl_create(C.byref(cfg), C.byref(h)) == 0
@@ -51,7 +52,10 @@ def main():
         if name.endswith('+final'):
             t['final'] = torch.zeros(n, obs_dim, device='cuda'); t['trunc'] = torch.zeros(n, dtype=torch.uint8, device='cuda')
             b.final_obs = t['final'].data_ptr(); b.truncated = t['trunc'].data_ptr()
-        L.hrl_reset(h, C.byref(b), None, None)
+        if name.endswith('+contacts'):   # the longer record (hrl_buffers_ext); every other variant is handed the plain v7 record, which older builds know
+            t['contacts'] = torch.zeros(n, K.HRL_CONTACTS_STRIDE, device='cuda')
+            b = K.hrl_buffers_ext.of(b); b.contacts = t['contacts'].data_ptr()
+        assert L.hrl_reset(h, C.byref(b), None, None) == 0, L.hrl_last_error()
         for k in range(settle):
             b.actions = acts[k % 64].data_ptr(); L.hrl_step(h, C.byref(b), None)
         envs[name] = (L, h, b, t)
