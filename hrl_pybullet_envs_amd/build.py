@@ -1,4 +1,5 @@
-"""Build the gfx950 HIP library in-tree: hrl_pybullet_envs_amd/libhrl_envs_hip.so.
+"""Build the gfx950 HIP libraries in-tree: hrl_pybullet_envs_amd/libhrl_envs_hip.so (the step, include/hrl_envs.h) and
+hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -10,6 +11,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libhrl_envs_hip.so')
 SOURCES = ['hrl_hip.hip', 'step_core.h', 'host_cfg.h']
+RENDER_LIB = os.path.join(PKG, 'libhrl_render_hip.so')
+RENDER_SOURCES = ['render_hip.hip', 'render_core.h', 'step_core.h', 'host_cfg.h']   # a library of its own: the step library's code object stays what it was
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -25,25 +28,38 @@ def kernel_source_hash():
     return h.hexdigest()
 
 
-def _stale():
-    if not os.path.exists(LIB):
+def _stale(lib=LIB, sources=SOURCES, headers=('hrl_envs.h',)):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(PKG, '..', 'include', 'hrl_envs.h'), os.path.abspath(__file__)]  # this file holds the flags
+    t = os.path.getmtime(lib)
+    deps = [os.path.join(CSRC, s) for s in sources] + [os.path.join(PKG, '..', 'include', h) for h in headers] + [os.path.abspath(__file__)]  # this file holds the flags
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False):
-    if not force and not _stale():
-        return LIB
+def _compile(lib, source, verbose):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    cmd = [hipcc] + HIPCC_FLAGS + ['-o', LIB, os.path.join(CSRC, 'hrl_hip.hip')]
+    cmd = [hipcc] + HIPCC_FLAGS + ['-o', lib, os.path.join(CSRC, source)]
     if verbose:
         cmd.insert(1, '-Rpass-analysis=kernel-resource-usage')
         print(' '.join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
+    return lib
+
+
+def build_render(force=False, verbose=False):
+    if not force and not _stale(RENDER_LIB, RENDER_SOURCES, ('hrl_envs.h', 'hrl_render.h')):
+        return RENDER_LIB
+    return _compile(RENDER_LIB, 'render_hip.hip', verbose)
+
+
+def build(force=False, verbose=False):
+    """Both libraries; returns the step library's path."""
+    if force or _stale():
+        _compile(LIB, 'hrl_hip.hip', verbose)
+    build_render(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
+    print(RENDER_LIB)

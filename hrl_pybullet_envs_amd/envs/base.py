@@ -197,6 +197,11 @@ class BatchedGymEnv:
             env.record_contacts()
         return contacts.as_list(env.contacts, index)
 
+    def render_batch(self, view=None, mask=None, out=None):
+        """A top-down RGB image of EVERY env in one launch: torch.uint8 [N, H, W, 3] on the env's device (BatchedEnv.render,
+        render_device.default_view for other views).  `render(mode='rgb_array')` stays the host-drawn picture of one env."""
+        return self._backend().render(view, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

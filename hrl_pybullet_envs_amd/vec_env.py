@@ -141,6 +141,28 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
+    def render(self, view=None, mask=None, out=None):
+        """A top-down RGB image of every env: torch.uint8 [N, H, W, 3] on this device, from ONE launch on the current stream (render_device.py,
+        include/hrl_render.h) -- what a high-level policy's CNN or a video writer reads without leaving HBM.  `view`: an hrl_view
+        (render_device.default_view(cfg, mode, width, height)); None = the 64 x 64 world view of the whole arena.  Envs with mask[i] == 0 keep
+        the bytes `out` holds (zeros in a fresh tensor).  `out` is reused when given (uint8, [N, H, W, 3], contiguous).  The picture is of
+        the state / items / aux tensors as they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import render_device as R
+        if view is None:
+            view = getattr(self, '_default_view', None)
+            if view is None:
+                view = self._default_view = R.default_view(self.cfg)
+        if out is None:
+            make = torch.empty if mask is None else torch.zeros
+            out = make(self.num_envs, view.height, view.width, 3, dtype=torch.uint8, device=self.device)
+        else:
+            R.check_out(out, self.num_envs, view, self.device)
+        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            R.render(self.cfg, self._bufs_ref, view, None if m is None else m.data_ptr(), out, self._stream())
+        self._last_render_mask = m  # keep alive until the stream has consumed it
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
