@@ -43,8 +43,14 @@ def mismatches(got, want, tol=TOL):
     return int(np.sum(np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64)) > tol))
 
 
+def observed(s):
+    obs = s.observe().copy()
+    s.close()
+    return obs
+
+
 def replay_all(make_side, default_config):
-    """make_side(cfg) -> object with .n, .set(qpos, qvel, items=None, aux3=None, initial_z=None) and .observe() -> obs [n, D] numpy.
+    """make_side(cfg) -> a backend of tests/backends.py: .set(qpos, qvel, items=None, aux3=None, initial_z=None), .observe() -> obs [n, D] numpy, .close().
     Returns {fixture: (cases, readings compared, readings off by more than TOL)}."""
     report = {}
 
@@ -66,7 +72,7 @@ def replay_all(make_side, default_config):
         s = make_side(cfg)
         qpos, qvel = pose_rows(n, [c['pos'] for c in cs], [(0.0, 0.0, c['yaw']) for c in cs])
         s.set(qpos, qvel)
-        obs = s.observe()
+        obs = observed(s)
         for i, c in enumerate(cs):
             off += mismatches(obs[i, lo:lo + bins], c['out']); readings += bins
         cases += n
@@ -86,7 +92,7 @@ def replay_all(make_side, default_config):
             qpos, qvel = pose_rows(n, [c['robot_xy'] for c in cs], [(0.0, 0.0, c['yaw']) for c in cs], z=0.75 if kind == K.HRL_ANT_GATHER else 0.5)
             items = np.array([np.array(c['food'] + c['poison'], np.float64).reshape(-1) for c in cs], np.float32)
             s.set(qpos, qvel, items=items)
-            obs = s.observe()
+            obs = observed(s)
             for i, c in enumerate(cs):
                 if use_sensor:
                     want = c['food_readings'] + c['poison_readings']
@@ -110,7 +116,7 @@ def replay_all(make_side, default_config):
         s = make_side(cfg)
         qpos, qvel = pose_rows(n, [c['torso_xy'] for c in cs], [c['rpy'] for c in cs], z=0.45)
         s.set(qpos, qvel, aux3=np.array([tgt_index[tuple(c['target'])] for c in cs], np.int32))
-        obs = s.observe()
+        obs = observed(s)
         for i, c in enumerate(cs):
             if not st:
                 off += mismatches(obs[i, 26:28], c['target_vec_obs']); readings += 2
@@ -124,7 +130,7 @@ def replay_all(make_side, default_config):
         s = make_side(cfg)
         qpos, qvel = pose_rows(1, [(0.3, -0.2)], [(0.0, 0.0, 0.4)], z=0.5)
         s.set(qpos, qvel, aux3=np.array([3], np.int32))
-        off += mismatches(s.observe()[0, 26:28], spot[key]); readings += 2; cases += 1
+        off += mismatches(observed(s)[0, 26:28], spot[key]); readings += 2; cases += 1
     report['maze_target_and_walls'] = (cases, readings, off)
 
     # ---- point_bot.py:48-67 PointBot.calc_state (cases whose rpy is the canonical Euler triple of its rotation: |pitch| < pi / 2)
@@ -134,7 +140,7 @@ def replay_all(make_side, default_config):
     s = make_side(cfg)
     qpos, qvel = pose_rows(n, [c['xyz'][:2] for c in cs], [c['rpy'] for c in cs], z=[c['xyz'][2] for c in cs], vel=[c['speed'] for c in cs])
     s.set(qpos, qvel, items=np.full((n, 32), 40.0, np.float32), initial_z=1.0)
-    obs = s.observe()
+    obs = observed(s)
     off = sum(mismatches(obs[i, 0:8], c['out'], 5e-5) for i, c in enumerate(cs))   # 0.3 * |v| up to 2.6: a few fp32 ulps more
     report['pointbot_state'] = (n, 8 * n, off)
     return report

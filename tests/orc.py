@@ -116,6 +116,17 @@ class OracleEnv:
         fn('orc_observe_batch', self.dtype)(C.byref(self.cfg), ptr(self.state), ptr(self.items), ptr(self.aux), ptr(m), ptr(self.obs))
         return self.obs
 
+    def set_goals(self, goals, mask=None):
+        """AntFlagrun with flag_manual_goals: `env.goals = [...]; env.next_target()`, goals [N, n_goals, 2]"""
+        g = np.ascontiguousarray(goals, self.dtype)
+        fn('orc_set_goals_batch', self.dtype)(C.byref(self.cfg), ptr(self.state), ptr(self.items), ptr(self.aux), ptr(g), g.shape[1], ptr(mask), ptr(self.obs))
+
+    def next_target(self, mask=None):
+        """`env.next_target()` of every (masked) env; ok[i] == 0 where the reference raises IndexError, 1 where mask[i] == 0"""
+        ok = np.ones(self.N, np.uint8)
+        fn('orc_next_target_batch', self.dtype)(C.byref(self.cfg), ptr(self.state), ptr(self.items), ptr(self.aux), ptr(mask), ptr(self.obs), ptr(ok))
+        return ok
+
     @property
     def qpos(self):
         return self.state[:, :15]

@@ -2,40 +2,21 @@
 The same replay through the C-ABI on the device: tests/test_gpu_golden.py."""
 import numpy as np
 
-import emu_env
 import golden_replay
 import orc
+from backends import Emu
 from hrl_pybullet_envs_amd import _capi as K
 
 
-class EmuSide:
-    def __init__(self, cfg):
-        self.e = emu_env.EmuEnv(cfg)
-        self.n = cfg.num_envs
-
-    def set(self, qpos, qvel, items=None, aux3=None, initial_z=None):
-        e = self.e
-        e.state[:, 0:15] = qpos; e.state[:, 15:29] = qvel
-        if initial_z is not None:
-            e.state[:, K.HRL_INITZ_OFF] = initial_z
-        if items is not None:
-            e.items[:, :items.shape[1]] = items
-        if aux3 is not None:
-            e.aux[:, 3] = aux3
-
-    def observe(self):
-        return self.e.observe().copy()
-
-
 def test_reference_fixtures_on_the_wave_phases():
-    golden_replay.check(golden_replay.replay_all(EmuSide, orc.default_config))
+    golden_replay.check(golden_replay.replay_all(Emu, orc.default_config))
 
 
 def test_observe_writes_nothing_but_the_observation():
     """hrl_observe: state, items, counters untouched; masked rows keep their observation; equal to the oracle's make_obs bit for bit."""
     for kind in (K.HRL_ANT_GATHER, K.HRL_ANT_MAZE, K.HRL_POINT_GATHER, K.HRL_ANT_FLAT, K.HRL_ANT_MAZE_MJ, K.HRL_ANT_FLAGRUN):
         cfg = orc.default_config(kind, num_envs=16, seed=5, auto_reset=1)
-        o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+        o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
         o.reset(); e.reset()
         rng = np.random.RandomState(kind)
         for t in range(5):

@@ -9,70 +9,39 @@ import pytest
 
 import emu_env
 import orc
+import parity_cases as P
+from backends import Emu, same
 from hrl_pybullet_envs_amd import _capi as K
 
 KINDS = [K.HRL_ANT_FLAT, K.HRL_ANT_GATHER, K.HRL_ANT_MAZE, K.HRL_POINT_GATHER, K.HRL_ANT_MAZE_MJ, K.HRL_ANT_FLAGRUN]
+REFUSED = dict(expected_exception=ValueError)   # what the adapter raises where the host executor refuses a goal list
+
+
+def make(kind, count_rows=False, **over):
+    """the sides tests/parity_cases.py drives: the host executor in both lane orders (it counts solver rows anyway)"""
+    return [Emu(Emu.config(kind, **over)), Emu(Emu.config(kind, **over), reverse=True)]
 
 
 @pytest.mark.parametrize('kind', KINDS)
 def test_reset_bit_exact(kind):
-    cfg = orc.default_config(kind, num_envs=64, seed=7)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-    o.reset(); e.reset()
-    assert np.array_equal(o.state, e.state) and np.array_equal(o.items, e.items) and np.array_equal(o.aux, e.aux)
-    assert np.array_equal(o.obs, e.obs)
-    # masked reset touches only the selected envs
-    mask = np.zeros(64, np.uint8); mask[::3] = 1
-    s0 = e.state.copy()
-    e.reset(mask); o.reset(mask)
-    assert np.array_equal(e.state[mask == 0], s0[mask == 0]) and np.array_equal(o.state, e.state)
-    assert np.all(e.aux[mask == 1, 2] == 2) and np.all(e.aux[mask == 0, 2] == 1)
+    P.reset(make, kind, 64, every=3, seed=7)
 
 
 @pytest.mark.parametrize('kind', KINDS)
 def test_free_running_bit_exact(kind):
     """Both implementations run free (no state copying) for 120 steps with auto-reset and a short time limit."""
-    n = 24
-    cfg = orc.default_config(kind, num_envs=n, seed=3, auto_reset=1, max_episode_steps=50)
-    o, e, er = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg), emu_env.EmuEnv(cfg, reverse=True)
-    o.reset(); e.reset(); er.reset()
-    rng = np.random.RandomState(kind)
-    for t in range(120):
-        a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-        if kind == K.HRL_POINT_GATHER and t == 7:
-            a[0] = 0  # point_bot.py:29 divides by |a| -> NaN -> done -> auto-reset
-        o.step(a); e.step(a); er.step(a)
-        for name in ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info'):
-            x, y, z = getattr(o, name), getattr(e, name), getattr(er, name)
-            assert np.array_equal(x, y, equal_nan=True), (t, name)
-            assert np.array_equal(y, z, equal_nan=True), (t, name, 'lane-order dependence')
-    assert o.aux[:, 2].min() >= 3  # every env went through at least two auto-resets
+    P.free_running(make, kind, 24, 120, stream=kind, min_episodes=3, seed=3, max_episode_steps=50)   # every env went through at least two auto-resets
 
 
 def test_gather_pickups_happen_and_match():
     """Drive the ants onto food: pickup, respawn draws and rewards must match exactly."""
-    n = 32
-    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=11, auto_reset=1)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-    o.reset(); e.reset()
-    rng = np.random.RandomState(5)
-    picked = 0
-    for t in range(40):
-        # teleport every torso next to one of its items (identical in both copies)
-        k = rng.randint(0, 16, n)
-        xy = o.items.reshape(n, 16, 2)[np.arange(n), k] + rng.uniform(-0.6, 0.6, (n, 2)).astype(np.float32)
-        o.state[:, 0:2] = xy; e.state[:, 0:2] = xy
-        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a)
-        picked += int((o.info[:, 0] != 0).sum())
-        assert np.array_equal(o.items, e.items) and np.array_equal(o.rew, e.rew) and np.array_equal(o.obs, e.obs)
-    assert picked > 50
+    P.gather_pickups(make, 32, 40, need=dict(picked=51))
 
 
 def test_maze_reaches_targets_and_matches():
     n = 32
     cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=2, auto_reset=1)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+    o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
     o.reset(); e.reset()
     rng = np.random.RandomState(9)
     hits = 0
@@ -93,7 +62,7 @@ def test_maze_reaches_targets_and_matches():
 def test_abs_pos_observation_variant(kind, n_bins, nf, npo):
     """use_sensor=False (ant_gather_env.py:179-196): nearest-first item coordinates instead of the bin sensor."""
     cfg = orc.default_config(kind, num_envs=16, seed=3, auto_reset=1, use_sensor=0, n_bins=n_bins, n_food=nf, n_poison=npo)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+    o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
     assert o.od == (26 if kind == K.HRL_ANT_GATHER else 8) + 2 * (min(nf, n_bins) + min(npo, n_bins))
     o.reset(); e.reset()
     assert np.array_equal(o.obs, e.obs)
@@ -115,7 +84,7 @@ def test_flagrun_goals_rewards_and_exhaustion():
     import ctypes as C
     n = 16
     cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=6, auto_reset=1, flag_max_targets=4, use_sensor=1)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+    o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
     o.reset(); e.reset()
     rng = np.random.RandomState(3)
     hits = dones = 0
@@ -140,7 +109,7 @@ def test_flagrun_close_goal_mode():
     n = 16
     cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=11, auto_reset=1, flag_max_targets=0, flag_max_target_dist=3.0,
                              flag_timeout=7)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+    o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
     o.reset(); e.reset()
     assert np.array_equal(o.items, e.items) and np.array_equal(o.obs, e.obs)
     g0 = o.items[:, 0:2].copy()
@@ -199,56 +168,14 @@ def test_product_defaults_equal_oracle_defaults():
         assert emu_env.lib().emu_obs_dim(C.byref(a)) == orc.obs_dim(a) == {0: 29, 1: 46, 2: 38, 3: 18, 4: 60, 5: 28}[kind]
 
 
-@pytest.mark.parametrize('kind,n,kw', [
-    (K.HRL_ANT_GATHER, 5, dict(n_bins=7, n_food=5, n_poison=3, sensor_range=9.0, sensor_span=2.0, world_size=(9.0, 11.0))),
-    (K.HRL_ANT_GATHER, 4, dict(respawn=0, robot_coll_dist=4.0, dying_cost=-3.0)),
-    (K.HRL_ANT_MAZE, 6, dict(sense_target=1, n_bins=8)),
-    (K.HRL_ANT_MAZE, 5, dict(target_encoding=1, sense_walls=0, tol=3.0, targ_dist_rew=1, max_steps=20, done_at_target=0)),
-    (K.HRL_ANT_MAZE_MJ, 4, dict(inner_rew_weight=0.5, n_bins=6)),
-    (K.HRL_ANT_GATHER, 3, dict(model_solver_iters=2, model_frame_skip=2, model_limit_margin=0.1)),
-    (K.HRL_ANT_GATHER, 6, dict(model_self_collision=0, model_item_collision=0)),
-    # hrl_model of ABI v7, all on at once: Bullet's per-body damping (pybullet's 0.04 and a strong one), restitution, a tight contact cap, joint damping + armature
-    (K.HRL_ANT_GATHER, 6, dict(model_linear_damping=0.04, model_angular_damping=0.04, model_restitution=0.3, model_max_contacts=6, model_joint_damping=1.0, model_joint_armature=1.0)),
-    (K.HRL_ANT_MAZE, 5, dict(model_linear_damping=3.0, model_angular_damping=8.0, model_restitution_threshold=0.0, model_restitution=0.8)),
-    (K.HRL_POINT_GATHER, 6, dict(model_linear_damping=0.04, model_angular_damping=2.0, model_restitution=0.5, model_max_contacts=3)),
-    (K.HRL_ANT_GATHER, 6, dict(robot_coll_dist=0.0)),
-    (K.HRL_POINT_GATHER, 6, dict(robot_coll_dist=-1.0, respawn=0)),
-    (K.HRL_ANT_MAZE, 5, dict(inner_rew_weight=1.0)),
-    (K.HRL_ANT_FLAGRUN, 7, dict(flag_max_targets=0, flag_max_target_dist=2.5, flag_timeout=6, flag_size=3.0, world_size=(5.0, 5.0), centroid_static_sum=(-2.5, 0.0))),
-    (K.HRL_ANT_FLAGRUN, 6, dict(flag_enclosed=0, centroid_n_static=1, centroid_static_sum=(0.0, 0.0), flag_timeout=8, flag_max_targets=5)),
-    (K.HRL_ANT_FLAGRUN, 6, dict(flag_switch_on_collision=0, flag_timeout=7, flag_max_targets=4)),
-    # constructor arguments beyond the caps of ABI <= 5 (ant_gather_env.py:16-29 takes any n_food / n_poison / n_bins, ant_maze_bullet_env.py:23
-    # any targets): more than 16 items (longer items record, 16-item slices in the packed contact phase, 6-bit item field of the respawn key),
-    # observations wider than the wave (several packing / store passes), more than 8 targets
-    (K.HRL_ANT_GATHER, 6, dict(n_food=20, n_poison=12, n_bins=24, world_size=(9.0, 9.0))),
-    (K.HRL_POINT_GATHER, 6, dict(n_food=20, n_poison=12, n_bins=24, world_size=(9.0, 9.0))),
-    (K.HRL_ANT_GATHER, 5, dict(n_food=40, n_poison=24, n_bins=64, robot_coll_dist=0.0, world_size=(8.0, 8.0))),
-    (K.HRL_POINT_GATHER, 5, dict(n_food=33, n_poison=31, n_bins=40, robot_coll_dist=-1.0, world_size=(8.0, 8.0))),
-    (K.HRL_ANT_GATHER, 5, dict(n_food=20, n_poison=12, n_bins=24, use_sensor=0, world_size=(9.0, 9.0))),
-    (K.HRL_ANT_MAZE_MJ, 4, dict(n_bins=16)),
-    (K.HRL_ANT_MAZE_MJ, 4, dict(n_bins=64)),
-    (K.HRL_ANT_MAZE, 6, dict(sense_target=1, n_bins=33, targets=[(-2.0 + 0.5 * i, -4.0 + 0.1 * i) for i in range(12)], tol=0.7)),
-    (K.HRL_ANT_FLAGRUN, 4, dict(use_sensor=1, n_bins=40, flag_timeout=9)),
-])
+# the emulator's own order of tests/parity_cases.py::CONFIG_MATRIX (the collected ids carry the position): the 25 entries it has always run, then the
+# 11 that only the device ran
+EMU_ORDER = [31, 1, 4, 5, 6, 10, 11, 12, 13, 14, 15, 16, 17, 8, 19, 20, 32, 33, 34, 25, 35, 27, 28, 29, 30, 0, 2, 3, 7, 9, 18, 21, 22, 23, 24, 26]
+
+
+@pytest.mark.parametrize('kind,n,kw', [(P.CONFIG_MATRIX[i][0], P.CONFIG_MATRIX[i][1], P.CONFIG_MATRIX[i][3]) for i in EMU_ORDER])
 def test_non_default_configs_bit_exact(kind, n, kw):
-    cfg = orc.default_config(kind, num_envs=n, seed=17, auto_reset=1, max_episode_steps=25, **kw)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-    o.reset(); e.reset()
-    rng = np.random.RandomState(4)
-    for t in range(60):
-        a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-        o.step(a); e.step(a)
-        for name in ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info', 'final_obs', 'truncated'):
-            assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (t, name)
-
-
-def both(cfg, reverse=False):
-    return orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg, reverse=reverse)
-
-
-def same(o, e, tag=''):
-    for name in ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info', 'final_obs', 'truncated'):
-        assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (tag, name)
+    P.config_matrix(make, kind, n, kw)
 
 
 @pytest.mark.parametrize('kind', [K.HRL_ANT_GATHER, K.HRL_POINT_GATHER])
@@ -256,54 +183,10 @@ def test_item_cubes_collide_and_contact_pickup(kind):
     """The food / poison cubes are static boxes (food.xml:12,19): robots parked on top of / next to cubes are pushed by
     them, and with robot_coll_dist <= 0 every contact point with a cube pays +-1 and moves it (ant_gather_env.py:113-116).
     Both lane orders of the wave phases equal the oracle bit for bit."""
-    n = 32
-    for kw in (dict(), dict(robot_coll_dist=0.0), dict(robot_coll_dist=0.0, use_sensor=0)):
-        cfg = orc.default_config(kind, num_envs=n, seed=13, auto_reset=1, **kw)
-        (o, e), er = both(cfg), emu_env.EmuEnv(cfg, reverse=True)
-        o.reset(); e.reset(); er.reset()
-        rng = np.random.RandomState(2)
-        touched = paid = 0
-        for t in range(30):
-            k = rng.randint(0, 16, n)
-            off = rng.uniform(-1.0, 1.0, (n, 2)).astype(np.float32) * (1.4 if kind == K.HRL_ANT_GATHER else 0.45)
-            if kw:  # contact mode: nothing is picked up by distance, so stand right next to / on the cube
-                xy = o.items.reshape(n, 16, 2)[np.arange(n), k] + off
-                for env in (o, e, er):
-                    env.state[:, 0:2] = xy
-                if kind == K.HRL_POINT_GATHER:
-                    # a player teleported INTO a cube is thrown out within a substep and touches nothing at the step's last collision
-                    # pass: park it at rest, unturned, with a face against the cube (gap -4 .. 12 mm) at any offset along that face
-                    side = rng.randint(0, 4, n); d = np.array([[1, 0], [-1, 0], [0, 1], [0, -1]], np.float32)[side]
-                    lat = rng.uniform(-0.42, 0.42, n).astype(np.float32); gap = rng.uniform(-0.004, 0.012, n).astype(np.float32)
-                    xy = o.items.reshape(n, 16, 2)[np.arange(n), k] - d * (np.float32(0.475) + gap)[:, None] + d[:, ::-1] * lat[:, None]
-                    for env in (o, e, er):
-                        env.state[:, 0:2] = xy; env.state[:, 2] = 0.35; env.state[:, 3:7] = [0, 0, 0, 1]; env.state[:, 7:13] = 0
-            a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-            it0 = o.items.copy()
-            o.step(a); e.step(a); er.step(a)
-            same(o, e, t); same(e, er, (t, 'lane order'))
-            paid += int((o.info[:, 0] != 0).sum()); touched += int(np.any(o.items != it0, axis=1).sum())
-            if 'use_sensor' in kw:  # get_food_obs (ant_gather_env.py:95-96) ran before reward_collision (:113-116) moved the cubes: old positions
-                live = np.isfinite(o.obs).all(axis=1) & (o.done == 0)
-                m, nb = min(8, cfg.n_bins), o.od - 4 * min(8, cfg.n_bins)
-                for i in np.nonzero(live)[0]:
-                    old = it0[i, :16].reshape(8, 2)
-                    assert all(any(np.array_equal(f, q) for q in old) for f in e.obs[i, nb:nb + 2 * m].reshape(m, 2)), (t, i)
-        if kw:
-            assert paid > 20 and touched > 20, (paid, touched)
-    # the cubes matter to the physics: the same rollout without them diverges
-    c1 = orc.default_config(kind, num_envs=n, seed=13, robot_coll_dist=0.0)
-    c0 = orc.default_config(kind, num_envs=n, seed=13, robot_coll_dist=4.0, respawn=0, model_item_collision=0)
-    o1, o0 = orc.OracleEnv(c1, np.float32), orc.OracleEnv(c0, np.float32)
-    o1.reset(); o0.reset()
-    # ant: the torso over the cube; point bot: one of its bottom corners over the cube (its contact points are the 8 corners)
-    xy = o1.items.reshape(n, 16, 2)[:, 3] + np.float32(0.05 if kind == K.HRL_ANT_GATHER else 0.33)
-    o1.state[:, 0:2] = xy; o0.state[:, 0:2] = xy; o0.items[...] = o1.items
-    if kind == K.HRL_ANT_GATHER:
-        o1.state[:, 2] = 0.4; o0.state[:, 2] = 0.4  # torso low enough to sit on the 0.225 m high cube
-    a = np.zeros((n, o1.ad), np.float32) + np.float32(0.3)
-    o1.step(a); o0.step(a)
-    assert np.abs(o1.state[:, :15] - o0.state[:, :15]).max() > 1e-3
+    P.item_cubes(make, kind, 32, 30, need={})
+    P.item_cubes(make, kind, 32, 30, need=dict(paid=21, touched=21), robot_coll_dist=0.0)
+    P.item_cubes(make, kind, 32, 30, need=dict(paid=21, touched=21), robot_coll_dist=0.0, use_sensor=0)
+    P.cubes_matter_to_the_physics(kind, 32)
 
 
 def test_pointbot_cube_corners_against_the_turned_player_box_bit_exact():
@@ -313,7 +196,7 @@ def test_pointbot_cube_corners_against_the_turned_player_box_bit_exact():
     import ctypes as C
     n = 48
     cfg = orc.default_config(K.HRL_POINT_GATHER, num_envs=n, seed=21, auto_reset=1, robot_coll_dist=0.0)
-    (o, e), er = both(cfg), emu_env.EmuEnv(cfg, reverse=True)
+    o, e, er = orc.OracleEnv(cfg, np.float32), Emu(cfg), Emu(cfg, reverse=True)
     o.reset(); e.reset(); er.reset()
     rng = np.random.RandomState(6)
     face_only = 0
@@ -346,28 +229,7 @@ def test_self_collision_rows_bit_exact_and_keep_legs_apart():
     """Hips forced far beyond their +-40 degree range so that capsules of different legs meet (within the range they
     cannot: step_core.h broad phase): the two-body rows of the wave phases equal the oracle's bit for bit in both lane
     orders, and the contacts push the legs apart again (with self-collision off they stay interpenetrated longer)."""
-    import ctypes as C
-    n = 48
-    cfg = orc.default_config(K.HRL_ANT_FLAT, num_envs=n, seed=5, auto_reset=0)
-    (o, e), er = both(cfg), emu_env.EmuEnv(cfg, reverse=True)
-    o.reset(); e.reset(); er.reset()
-    rng = np.random.RandomState(1)
-    seen = 0
-    for t in range(25):
-        if t % 5 == 0:
-            hips = rng.uniform(-1.5, 1.5, (n, 4)).astype(np.float32)
-            ank = rng.uniform(-1.8, 1.8, (n, 4)).astype(np.float32)
-            for env in (o, e, er):
-                env.state[:, 2] = 1.5; env.state[:, 7:15:2] = hips; env.state[:, 8:15:2] = ank; env.state[:, 15:29] = 0
-        # how many self contacts does the oracle see in these poses?
-        for i in range(0, n, 8):
-            q = o.state[i, :15].astype(np.float64); u = np.zeros(14); info = np.zeros(3, np.int32); dbg = np.zeros(13, np.int32)
-            orc.lib().orc_ant_substeps_items_f64(C.byref(cfg), orc.ptr(q), orc.ptr(u), orc.ptr(np.zeros(8)), 1, None, 0, orc.ptr(info), orc.ptr(dbg), None)
-            seen += int((dbg[1:] >= 64).sum())
-        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a); er.step(a)
-        same(o, e, t); same(e, er, (t, 'lane order'))
-    assert seen >= 10, seen  # sampled every 8th env: the rollouts really contain self contacts
+    P.self_collision(make, 48, 25, stride=8, need=dict(seen=10), auto_reset=0)
 
 
 def test_self_collision_broad_phase_is_exact():
@@ -399,127 +261,21 @@ def test_flagrun_manual_goals():
     """manual_goal_creation (ant_flagrun_env.py:27,150-153): reset draws no goal; `env.goals = [...]; env.next_target()` comes
     through hrl_set_goals (emu_set_goals here): as in the reference the list is consumed from its BACK (`goals.pop()`, :116) and
     the episode ends when it runs out; next_target() alone (hrl_next_target) pops one more, IndexError -> ok = 0."""
-    import ctypes as C
-    n, G = 8, 3
-    cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=6, auto_reset=0, flag_manual_goals=1, flag_timeout=0)
-    o, e = both(cfg)
-    o.reset(); e.reset()
-    same(o, e, 'reset')
-    assert np.all(o.items[:, 0] == 1000) and np.all(o.items[:, 1:] == 0) and np.all(o.aux[:, 3] == 0)  # upstream default walk target
-    goals = np.random.RandomState(0).uniform(-4, 4, (n, G, 2)).astype(np.float32)
-    orc.lib().orc_set_goals_batch_f32(C.byref(cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), orc.ptr(goals), G, None, orc.ptr(o.obs))
-    b = e._bufs()
-    assert emu_env.lib().emu_set_goals(C.byref(cfg), C.byref(b), orc.ptr(goals), G, None, 0) == 0
-    same(o, e, 'set_goals')
-    assert np.array_equal(o.items[:, 0:2], goals[:, G - 1]) and np.all((o.aux[:, 3] & 0xffff) == G - 1)  # the LAST goal first
-    P0 = K.HRL_FLAG_PENDING_OFF
-    assert np.array_equal(o.items[:, P0:P0 + 2 * (G - 1)], goals[:, :G - 1].reshape(n, -1))                # the rest, in list order
-    rng = np.random.RandomState(1)
-    visited = np.zeros(n, int); done_at = np.full(n, -1)
-    for t in range(12):
-        cur = o.items[:, 0:2].copy()
-        # walk_target_dist is measured from the parts centroid, which holds 13 robot parts and 2 static bodies (SURVEY A.5)
-        xy = ((15 * cur - np.array([-6.0, 0.0], np.float32)) / 13).astype(np.float32)
-        for env in (o, e):
-            env.state[:, 0:2] = xy; env.state[:, 2] = 0.5
-        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a)
-        same(o, e, t)
-        for i in range(n):
-            if done_at[i] < 0:
-                if o.rew[i] > 1000:
-                    visited[i] += 1
-                if visited[i] <= G - 1 and o.rew[i] > 1000 and not o.done[i]:
-                    assert np.array_equal(o.items[i, 0:2], goals[i, G - 1 - visited[i]])  # back to front
-                if o.done[i]:
-                    done_at[i] = t
-    assert np.all(visited >= G) and np.all(done_at >= 0)  # all goals reached, then the episode ends for lack of goals
-    # next_target() alone: one more goal assigned as plain data (env.goals = [g]), popped by hrl_next_target; then IndexError
-    extra = np.random.RandomState(3).uniform(-4, 4, (n, 2)).astype(np.float32)
-    ok_o = np.full(n, 7, np.uint8); ok_e = np.full(n, 7, np.uint8)
-    mask = np.ones(n, np.uint8); mask[5] = 0
-    for env in (o, e):
-        env.items[:, K.HRL_FLAG_PENDING_OFF:K.HRL_FLAG_PENDING_OFF + 2] = extra; env.aux[:, 3] = (env.aux[:, 3] & ~0xffff) | 1
-    for rep, want in ((0, 1), (1, 0)):
-        orc.lib().orc_next_target_batch_f32(C.byref(cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), orc.ptr(mask), orc.ptr(o.obs), orc.ptr(ok_o))
-        b = e._bufs()
-        assert emu_env.lib().emu_next_target(C.byref(cfg), C.byref(b), orc.ptr(mask), orc.ptr(ok_e), rep) == 0  # (second call: lanes in reverse order)
-        same(o, e, ('next_target', rep))
-        assert np.array_equal(ok_o, ok_e) and np.all(ok_o[mask == 1] == want) and ok_o[5] == 7
-        assert np.array_equal(o.items[mask == 1, 0:2], extra[mask == 1]) and np.all((o.aux[mask == 1, 3] & 0xffff) == 0)
-    assert not np.array_equal(o.items[5, 0:2], extra[5])  # the masked-out env kept its target
+    P.flagrun_manual_goals(make, 8, 3, skip=None, auto_reset=0)
 
 
 def test_flagrun_manual_close_targets():
     """manual_goal_creation with max_targets < 1 (ant_flagrun_env.py:113-114): next_target() -- from step() on reaching the goal /
     timing out, or from outside -- draws a goal near the robot whatever env.goals holds; reset() draws nothing (:150-153) and
     the episode never runs out of goals.  hrl_set_goals is refused there (the list would never be read)."""
-    import ctypes as C
-    n = 8
-    cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=9, auto_reset=0, flag_manual_goals=1, flag_max_targets=0,
-                             flag_max_target_dist=3.0, flag_timeout=4)
-    o, e = both(cfg)
-    o.reset(); e.reset()
-    same(o, e, 'reset')
-    assert np.all(o.items[:, 0] == 1000) and np.all(o.aux[:, 3] == 0)
-    ok_o = np.zeros(n, np.uint8); ok_e = np.zeros(n, np.uint8)
-    orc.lib().orc_next_target_batch_f32(C.byref(cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), None, orc.ptr(o.obs), orc.ptr(ok_o))
-    b = e._bufs()
-    assert emu_env.lib().emu_next_target(C.byref(cfg), C.byref(b), None, orc.ptr(ok_e), 0) == 0
-    same(o, e, 'next_target')
-    assert np.all(ok_o == 1) and np.all(ok_e == 1) and np.all((o.aux[:, 3] & 0xffff) == 1)
-    d = np.abs(o.items[:, 0:2] - o.state[:, 0:2])
-    assert np.all(d >= 0.5 - 1e-6) and np.all(d <= 1.5 + 1e-6) and np.all(np.abs(o.items[:, 0:2]) < 5)   # +-U(tol, mtd / 2) per axis, inside the arena
-    goals = np.zeros((n, 2, 2), np.float32)
-    assert emu_env.lib().emu_set_goals(C.byref(cfg), C.byref(b), orc.ptr(goals), 2, None, 0) != 0
-    rng = np.random.RandomState(2)
-    seen = [set() for _ in range(n)]
-    for t in range(14):  # the 4-step timeout retargets three times; nobody runs out of goals
-        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a)
-        same(o, e, t)
-        for i in range(n):
-            seen[i].add(tuple(o.items[i, 0:2]))
-    assert not o.done.any() and all(len(sx) >= 3 for sx in seen) and np.all((o.aux[:, 3] & 0xffff) >= 4)
+    P.flagrun_manual_close_targets(make, 8, 14, REFUSED, seed=9, auto_reset=0, flag_timeout=4)
 
 
 def test_flagrun_open_field_and_no_switch_on_collision():
     """ant_flagrun_env.py:59-64 `enclosed=False` (and no sensor): upstream's stadium scene, no walls -- an ant beyond where the
     arena's walls would stand meets nothing lateral; :183-194 `switch_flag_on_collision=False`: reaching the goal pays the +5000
     once and keeps the goal until the timeout moves it."""
-    n = 8
-    cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=3, auto_reset=0, flag_enclosed=0, centroid_n_static=1, centroid_static_sum=(0.0, 0.0),
-                             flag_switch_on_collision=0, flag_timeout=6, flag_max_targets=3)
-    walled = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=3, auto_reset=0, flag_switch_on_collision=0, flag_timeout=6, flag_max_targets=3)
-    o, e = both(cfg)
-    ow = orc.OracleEnv(walled, np.float32)
-    o.reset(); e.reset(); ow.reset()
-    same(o, e, 'reset')
-    for env in (o, e, ow):   # astride the line x = 6 where the enclosed arena's wall stands (world 12 x 12), feet on the ground
-        env.state[:, 0] = 6.0; env.state[:, 2] = 0.3
-    rng = np.random.RandomState(0)
-    for t in range(5):
-        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a); ow.step(a)
-        same(o, e, ('open', t))
-    assert np.isfinite(o.state).all() and np.all(np.abs(o.state[:, 0] - 6.0) < 0.5)   # nothing pushed it away
-    assert np.abs(ow.state[:, 0] - o.state[:, 0]).max() > 0.05                         # the walled arena did
-    o.reset(); e.reset()
-    paid = np.zeros(n, int); goals_seen = [set() for _ in range(n)]
-    for t in range(14):
-        g = np.zeros((n, 2), np.float32)
-        for i in range(n):
-            orc.lib().orc_flag_goal_f32(C.byref(cfg), int(o.aux[i, 2]), int(o.aux[i, 3] & 0xffff), orc.ptr(g[i:i + 1]))
-            goals_seen[i].add(tuple(g[i]))
-        xy = ((14 * g) / 13).astype(np.float32)   # centroid = (13 robot parts + the stadium's floor at the origin) / 14
-        for env in (o, e):
-            env.state[:, 0:2] = xy; env.state[:, 2] = 0.5
-        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a)
-        same(o, e, ('noswitch', t))
-        paid += (o.rew > 1000).astype(int)
-    # on the goal every step: paid once per goal, the goal only moves with the 6-step timeout (14 steps -> 3 goals), never `done` for it
-    assert np.all(paid == np.array([len(sx) for sx in goals_seen])) and all(len(sx) == 3 for sx in goals_seen), (paid, goals_seen)
+    P.flagrun_open_field_and_no_switch(make, 8, auto_reset=0)
 
 
 def test_reset_potential_is_taken_before_the_target_switch():
@@ -528,7 +284,7 @@ def test_reset_potential_is_taken_before_the_target_switch():
     dt = np.float32(0.0165 / 4) * 4
     for kind, kw in ((K.HRL_ANT_FLAGRUN, dict()), (K.HRL_ANT_MAZE, dict(inner_rew_weight=1.0)), (K.HRL_ANT_MAZE_MJ, dict(inner_rew_weight=1.0))):
         cfg = orc.default_config(kind, num_envs=6, seed=2, auto_reset=0, **kw)
-        o, e = both(cfg)
+        o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
         o.reset(); e.reset()
         same(o, e, 'reset 1')
         pot1 = o.state[:, 31].copy()
@@ -572,35 +328,7 @@ def test_envs_that_blow_up_match_too(kind, auto_reset):
     """Non-finite and absurd states -- velocities of 1e20 and inf, a NaN coordinate, a torso 1e19 m away, robots inside a wall, joint angles far
     out of range -- go through the same arithmetic in the wave phases and in the oracle: NaN, inf, done, the dying cost and the auto-reset that
     follows come out identical (NaNs compared as equal)."""
-    n = 64
-    cfg = orc.default_config(kind, num_envs=n, seed=31, auto_reset=auto_reset)
-    o, e = both(cfg)
-    o.reset(); e.reset()
-    rng = np.random.RandomState(9)
-    nq = 7 if kind == K.HRL_POINT_GATHER else 15
-    for t in range(15):
-        a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-        if t % 3 == 0:
-            rows = rng.permutation(n)[:48]
-            for env in (o, e):
-                r2 = np.random.RandomState(100 + t)
-                env.state[rows[0:8], 15 + r2.randint(0, 6, 8)] = 1e20
-                env.state[rows[8:16], 15 + r2.randint(0, 6, 8)] = np.inf
-                env.state[rows[16:24], 15 + r2.randint(0, 6, 8)] = -3e38
-                env.state[rows[24:28], 0] = 1e19
-                env.state[rows[28:32], 2] = -1e19
-                env.state[rows[32:36], r2.randint(0, nq, 4)] = np.nan
-                env.state[rows[36:40], 0:2] = [-2.0, 0.0] if kind in (K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ) else [7.6, 7.6]
-                if kind != K.HRL_POINT_GATHER:
-                    env.state[rows[40:48], 7 + r2.randint(0, 8, 8)] = r2.choice([40.0, -1e6, 3e30], 8)
-                if kind in (K.HRL_ANT_GATHER, K.HRL_POINT_GATHER):  # item coordinates too
-                    env.items[rows[0:4], r2.randint(0, 32, 4)] = np.nan
-                    env.items[rows[4:8], r2.randint(0, 32, 4)] = np.inf
-                    env.items[rows[24:26], r2.randint(0, 32, 2)] = 1e30
-                env.state[rows[20:24], 15 + r2.randint(0, 6, 4)] = np.nan
-                env.state[rows[26:28], 1] = -np.inf
-        o.step(a); e.step(a)
-        same(o, e, t)
+    P.blow_up(make, kind, 64, auto_reset)
 
 
 @pytest.mark.parametrize('kind', KINDS)
@@ -624,36 +352,7 @@ def test_terminal_observation_and_truncation_flag(kind):
     info['TimeLimit.truncated'] = not done).  Property, on the oracle: an auto-resetting env with a step limit against a twin without reset
     and without limit stepped from the same pre-step records -- the twin's observation IS the terminal one, its done the env's own.
     Then the wave phases (both lane orders) equal the oracle bit for bit, final_obs / truncated included (same())."""
-    n, limit = 24, 9
-    kw = dict(flag_timeout=4, flag_max_targets=3) if kind == K.HRL_ANT_FLAGRUN else {}
-    cfg = orc.default_config(kind, num_envs=n, seed=5, auto_reset=1, max_episode_steps=limit, **kw)
-    twin = orc.OracleEnv(orc.default_config(kind, num_envs=n, seed=5, auto_reset=0, max_episode_steps=0, **kw), np.float32)
-    (o, e), er = both(cfg), emu_env.EmuEnv(cfg, reverse=True)
-    o.reset(); e.reset(); er.reset()
-    rng = np.random.RandomState(8)
-    n_trunc = n_term = n_both = 0
-    for t in range(40):
-        if t % 4 == 3 or t % 9 == 8:   # some episodes end on their own -- a numerical failure ends any kind's (ant_gather_env.py:101-103,
-            rows = rng.permutation(n)[:4]   # gather_base.py:91-93), an ant held under 0.26 m dies --, some of them exactly at the step limit
-            for env in (o, e, er):
-                env.state[rows[:2], 15] = np.nan
-                if kind != K.HRL_POINT_GATHER:
-                    env.state[rows[2:], 2] = 0.05; env.state[rows[2:], 17] = -3.0
-        twin.state[...] = o.state; twin.items[...] = o.items; twin.aux[...] = o.aux
-        a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-        keep = o.final_obs.copy()
-        o.step(a); e.step(a); er.step(a); twin.step(a)
-        same(o, e, t); same(e, er, (t, 'lane order'))
-        d = o.done.astype(bool)
-        hit_limit = twin.aux[:, 0] >= limit
-        assert np.array_equal(d, twin.done.astype(bool) | hit_limit)
-        assert np.array_equal(o.truncated.astype(bool), hit_limit & ~twin.done.astype(bool))
-        assert np.array_equal(o.final_obs[d], twin.obs[d], equal_nan=True)         # the terminal observation
-        assert np.array_equal(o.final_obs[~d], keep[~d], equal_nan=True)            # rows of live envs are left alone
-        assert np.array_equal(o.rew, twin.rew, equal_nan=True)
-        assert not np.array_equal(o.final_obs[d], o.obs[d], equal_nan=True) or not d.any()   # obs itself is already the next episode's first
-        n_trunc += int(o.truncated.sum()); n_term += int((d & ~o.truncated.astype(bool)).sum()); n_both += int((hit_limit & twin.done.astype(bool)).sum())
-    assert n_trunc >= 20 and n_term >= 5 and n_both >= 1, (n_trunc, n_term, n_both)   # n_both: ended on its own AT the limit -> not truncated
+    P.terminal_observation(make, kind, 24, 4, need=dict(n_trunc=20, n_term=5, n_both=1))
 
 
 @pytest.mark.parametrize('kind,kw', [
@@ -666,79 +365,13 @@ def test_more_than_16_items(kind, kw):
     """n_food + n_poison > 16 (ant_gather_env.py:16-17 takes any counts): the longer items record, the 16-item slices of the packed
     contact phase, the wider item field of the respawn key and the item codes beyond the capsule pairs.  Robots are parked at every slot in
     turn so that the items past the 16th (and past the 48th) are picked up, touched and sensed; both lane orders equal the oracle."""
-    n = 32
-    n_items = kw['n_food'] + kw['n_poison']
-    cfg = orc.default_config(kind, num_envs=n, seed=19, auto_reset=1, **kw)
-    assert orc.items_stride(cfg) == (64 if n_items == 32 else 128)
-    (o, e), er = both(cfg), emu_env.EmuEnv(cfg, reverse=True)
-    o.reset(); e.reset(); er.reset()
-    same(o, e, 'reset')
-    assert np.all(o.items[:, 2 * n_items:] == 0) and np.all(np.abs(o.items[:, :2 * n_items]) <= 7.0) and np.all(o.items[:, 2 * n_items - 2:2 * n_items] != 0)
-    contact = 'robot_coll_dist' in kw
-    rng = np.random.RandomState(3)
-    paid_hi = moved_hi = 0
-    for t in range(36):
-        k = (np.arange(n) * 2 + t * 5) % n_items        # every slot gets its turn
-        it = o.items[:, :2 * n_items].reshape(n, n_items, 2)[np.arange(n), k]
-        if contact and kind == K.HRL_POINT_GATHER:
-            side = rng.randint(0, 4, n); d = np.array([[1, 0], [-1, 0], [0, 1], [0, -1]], np.float32)[side]
-            lat = rng.uniform(-0.3, 0.3, n).astype(np.float32); gap = rng.uniform(-0.004, 0.01, n).astype(np.float32)
-            xy = it - d * (np.float32(0.475) + gap)[:, None] + d[:, ::-1] * lat[:, None]
-            for env in (o, e, er):
-                env.state[:, 0:2] = xy; env.state[:, 2] = 0.35; env.state[:, 3:7] = [0, 0, 0, 1]; env.state[:, 7:13] = 0
-        else:
-            off = rng.uniform(-1.0, 1.0, (n, 2)).astype(np.float32) * np.float32(0.5 if not contact else 1.2)
-            for env in (o, e, er):
-                env.state[:, 0:2] = it + off
-        a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-        it0 = o.items.copy()
-        o.step(a); e.step(a); er.step(a)
-        same(o, e, t); same(e, er, (t, 'lane order'))
-        moved = np.any((o.items != it0).reshape(n, -1, 2), axis=2) & ~o.done.astype(bool)[:, None]
-        moved_hi += int(moved[:, 16:n_items].sum()) if n_items <= 48 else int(moved[:, 48:n_items].sum())
-        paid_hi += int((o.info[:, 0] != 0).sum())
-    assert moved_hi >= 10 and paid_hi >= 20, (moved_hi, paid_hi)
-    # the sensor sees the items past the 16th: with only those in range, readings are non-zero
-    if not contact:
-        o2 = orc.OracleEnv(orc.default_config(kind, num_envs=4, seed=1, **kw), np.float32)
-        e2 = emu_env.EmuEnv(o2.cfg)
-        o2.reset(); e2.reset()
-        for env in (o2, e2):
-            env.items[:, :32] = 90.0       # the first 16 far out of range
-            env.items[:, 32:2 * n_items:2] = env.state[:, 0:1] + 3.0; env.items[:, 33:2 * n_items:2] = env.state[:, 1:2] + np.linspace(-2, 2, n_items - 16, dtype=np.float32)
-        a = np.zeros((4, o2.ad), np.float32) + np.float32(0.1)
-        o2.step(a); e2.step(a)
-        same(o2, e2, 'sensor')
-        nb = 26 if kind == K.HRL_ANT_GATHER else 8
-        assert (o2.obs[:, nb:] > 0).any(axis=1).all()
+    P.more_than_16_items(make, kind, 32, 36, need=dict(moved_hi=10, paid=20), **kw)
 
 
 def test_manual_goal_lists_longer_than_15():
     """manual_goal_creation with flag_goal_capacity = 40 (`env.goals = [...]` takes any list, ant_flagrun_env.py:45): the pending list lives in a
     longer items record; 40 goals are consumed back to front, one per 3-step timeout."""
-    import ctypes as C
-    n, G = 6, 40
-    cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=2, auto_reset=0, flag_manual_goals=1, flag_goal_capacity=G, flag_timeout=3, max_episode_steps=0)
-    assert orc.items_stride(cfg) == 96
-    (o, e), er = both(cfg), emu_env.EmuEnv(cfg, reverse=True)
-    o.reset(); e.reset(); er.reset()
-    goals = np.random.RandomState(0).uniform(-4, 4, (n, G, 2)).astype(np.float32)
-    orc.lib().orc_set_goals_batch_f32(C.byref(cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), orc.ptr(goals), G, None, orc.ptr(o.obs))
-    for env in (e, er):
-        b = env._bufs()
-        assert emu_env.lib().emu_set_goals(C.byref(cfg), C.byref(b), orc.ptr(goals), G, None, env.reverse) == 0
-    same(o, e, 'set_goals'); same(e, er, 'set_goals lane order')
-    assert np.array_equal(o.items[:, 0:2], goals[:, G - 1]) and np.all((o.aux[:, 3] & 0xffff) == G - 1)
-    assert emu_env.lib().emu_set_goals(C.byref(cfg), C.byref(e._bufs()), orc.ptr(goals), G + 1, None, 0) != 0   # beyond the capacity
-    rng = np.random.RandomState(1)
-    for t in range(3 * G + 2):
-        a = rng.uniform(-0.3, 0.3, (n, 8)).astype(np.float32)
-        o.step(a); e.step(a); er.step(a)
-        same(o, e, t); same(e, er, (t, 'lane order'))
-        left, cur = G - 1 - (t + 1) // 3, o.aux[:, 3] & 0xffff   # one goal per timeout, sooner where a goal happens to be reached
-        live = ~o.done.astype(bool)
-        assert np.all(cur[live] <= max(left, 0)) and np.array_equal(o.items[live, 0:2], goals[np.arange(n)[live], cur[live]]), t
-    assert o.done.all()    # the list ran out (IndexError in the reference, :193-194)
+    P.manual_goal_lists_longer_than_15(make, 6, REFUSED, auto_reset=0)
 
 
 def test_next_target_pops_the_shared_list_of_a_non_manual_env():
@@ -747,15 +380,13 @@ def test_next_target_pops_the_shared_list_of_a_non_manual_env():
     import ctypes as C
     n = 9
     cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=4, auto_reset=0, flag_max_targets=3)
-    o, e = both(cfg)
+    o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
     o.reset(); e.reset()
     mask = np.ones(n, np.uint8); mask[::4] = 0
     for k in range(4):
-        ok_o, ok_e = np.full(n, 7, np.uint8), np.full(n, 7, np.uint8)
-        orc.lib().orc_next_target_batch_f32(C.byref(cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), orc.ptr(mask), orc.ptr(o.obs), orc.ptr(ok_o))
-        assert emu_env.lib().emu_next_target(C.byref(cfg), C.byref(e._bufs()), orc.ptr(mask), orc.ptr(ok_e), 0) == 0
+        ok_o, ok_e = o.next_target(mask), e.next_target(mask)
         same(o, e, k)
-        assert np.array_equal(ok_o, ok_e) and np.all(ok_o[mask == 0] == 7) and np.all(ok_o[mask == 1] == (1 if k < 2 else 0))
+        assert np.array_equal(ok_o, ok_e) and np.all(ok_o[mask == 0] == 1) and np.all(ok_o[mask == 1] == (1 if k < 2 else 0))
         assert np.all((o.aux[mask == 1, 3] & 0xffff) == min(2 + k, 3)) and np.all((o.aux[mask == 0, 3] & 0xffff) == 1)
     a = np.zeros((n, 8), np.float32)
     o.step(a); e.step(a)
@@ -780,49 +411,11 @@ def test_random_legal_configs():
     assert ended > 1000
 
 
-def _item_boxes(o, i):
-    ni = o.cfg.n_food + o.cfg.n_poison
-    it = o.items[i, :2 * ni].reshape(ni, 2).astype(np.float64)
-    return {(16 + k if k < 48 else 64 + k): (np.r_[it[k] - 0.125, -0.025], np.r_[it[k] + 0.125, 0.225]) for k in range(ni)}
-
-
 def test_capsule_mid_sections_against_cubes_and_the_maze_box():
     """assets/ant.xml:16-55 capsules against assets/food.xml:12 cubes and the assets/box.xml:12 maze box: ants let down onto cubes with the
     MIDDLE of their feet (contact pickup, ant_gather_env.py:113-116: the touch is paid) and feet laid across the vertical edges of the maze
     box -- contacts no end-point sphere sees; wave phases == oracle bit for bit."""
-    import capsule_cases as cc
-    n = 32
-    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=4, auto_reset=1, robot_coll_dist=0.0)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-    o.reset(); e.reset()
-    rng = np.random.RandomState(8)
-    paid = mid = 0
-    for t in range(6):
-        cc.cubes_under_the_feet(o, rng)
-        mid += cc.count_mid_section_contacts(o, range(0, n, 4), lambda i: _item_boxes(o, i))
-        e.state[...] = o.state; e.items[...] = o.items; e.aux[...] = o.aux
-        for k in range(2):
-            a = (rng.uniform(-1, 1, (n, 8)) * (0.0 if k == 0 else 0.3)).astype(np.float32)
-            o.step(a); e.step(a)
-            for name in ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info'):
-                assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (t, k, name)
-            paid += int((o.info[:, 0] != 0).sum())
-    assert mid >= 20 and paid >= 60, (mid, paid)
-    cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=4, auto_reset=1)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-    o.reset(); e.reset()
-    box = {8: (np.array([-5., -2, 0]), np.array([1., 2, 2]))}
-    mid = 0
-    for t in range(6):
-        cc.foot_across_the_maze_corner(o, rng)
-        mid += cc.count_mid_section_contacts(o, range(0, n, 2), lambda i: box)
-        e.state[...] = o.state; e.aux[...] = o.aux
-        for k in range(2):
-            a = (rng.uniform(-1, 1, (n, 8)) * 0.3).astype(np.float32)
-            o.step(a); e.step(a)
-            for name in ('state', 'aux', 'obs', 'rew', 'done', 'info'):
-                assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (t, k, name)
-    assert mid >= 25, mid
+    P.capsule_mid_sections(make, 32, rounds=6, steps=2, stride=4, need=dict(mid=20, paid=60, mid_box=25))
 
 
 def test_feet_contact_flags_show_the_previous_step():
@@ -832,7 +425,7 @@ def test_feet_contact_flags_show_the_previous_step():
     a step ride in bits 28..31 of aux[1]."""
     for kind, lo in ((K.HRL_ANT_MAZE, 22), (K.HRL_ANT_FLAGRUN, 24)):
         cfg = orc.default_config(kind, num_envs=6, seed=2, auto_reset=1, max_episode_steps=30)
-        o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+        o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
         o.reset(); e.reset()
         assert np.all(o.obs[:, lo:lo + 4] == 0) and np.all((o.aux[:, 1].view(np.uint32) >> 28) == 0)
         seen = 0
@@ -862,7 +455,7 @@ def test_flagrun_path_reward_switched_on_for_a_live_env():
     of a default env was all zeros and the first steps after the switch paid +-inf (x / 0) until the next goal or reset."""
     n = 12
     cfg = orc.default_config(K.HRL_ANT_FLAGRUN, num_envs=n, seed=9, auto_reset=1, flag_timeout=25, max_episode_steps=2000)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+    o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
     o.reset(); e.reset()
     assert np.all(o.items[:, K.HRL_FLAG_SQDIST_OFF] >= 0.25) and np.all(o.items[:, K.HRL_FLAG_START_OFF:K.HRL_FLAG_START_OFF + 2] == 0)   # goals >= 0.5 from the start (:71-78)
     rng = np.random.RandomState(1)
@@ -927,39 +520,8 @@ def test_second_support_points_of_capsules_lying_flat_on_a_box_face():
     """A capsule that rests flat on a face of the maze box (assets/box.xml:12) or on the top of an item cube (assets/food.xml:12) gets a SECOND support
     point (Bullet keeps a manifold there; with one point the capsule rocks): feet hanging alongside the box's vertical faces, legs stretched out level
     over cubes -- states full of such contacts, counted; wave phases == oracle bit for bit, the contact cap included."""
-    import capsule_cases as cc
-    n = 32
-    rng = np.random.RandomState(12)
-    for cap in (12, 5):
-        cfg = orc.default_config(K.HRL_ANT_MAZE, num_envs=n, seed=4, auto_reset=1, model_max_contacts=cap)
-        o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-        o.reset(); e.reset()
-        seconds = 0
-        for t in range(4):
-            cc.feet_flat_against_the_maze_box(o, rng)
-            seconds += cc.count_second_points(o, range(n))
-            e.state[...] = o.state; e.aux[...] = o.aux
-            for k in range(2):
-                a = (rng.uniform(-1, 1, (n, 8)) * 0.3).astype(np.float32)
-                o.step(a); e.step(a)
-                for name in ('state', 'aux', 'obs', 'rew', 'done', 'info', 'solver_rows'):
-                    assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (cap, t, k, name)
-        assert seconds >= (60 if cap == 12 else 10), (cap, seconds)
-    cfg = orc.default_config(K.HRL_ANT_GATHER, num_envs=n, seed=4, auto_reset=1, robot_coll_dist=0.0)
-    o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
-    o.reset(); e.reset()
-    seconds = paid = 0
-    for t in range(4):
-        cc.feet_flat_on_cubes(o, rng)
-        seconds += cc.count_second_points(o, range(n))
-        e.state[...] = o.state; e.items[...] = o.items; e.aux[...] = o.aux
-        for k in range(2):
-            a = (rng.uniform(-1, 1, (n, 8)) * 0.2).astype(np.float32)
-            o.step(a); e.step(a)
-            for name in ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info', 'solver_rows'):
-                assert np.array_equal(getattr(o, name), getattr(e, name), equal_nan=True), (t, k, name)
-            paid += int((o.info[:, 0] != 0).sum())
-    assert seconds >= 100 and paid >= 60, (seconds, paid)
+    P.second_support_points(make, 32, rounds=4, stride=1, maze=[(0, 12, dict(seconds=60)), (0, 5, dict(seconds=10))],
+                            gather=[(0, dict(seconds=100, paid=60))])
 
 
 def test_observe_shows_the_feet_flags_the_last_step_left():
@@ -968,7 +530,7 @@ def test_observe_shows_the_feet_flags_the_last_step_left():
     state it writes.  Wave phases == oracle, and both == the bits."""
     for kind, lo in ((K.HRL_ANT_MAZE, 22), (K.HRL_ANT_FLAGRUN, 24)):
         cfg = orc.default_config(kind, num_envs=8, seed=3, auto_reset=0, max_episode_steps=0)
-        o, e = orc.OracleEnv(cfg, np.float32), emu_env.EmuEnv(cfg)
+        o, e = orc.OracleEnv(cfg, np.float32), Emu(cfg)
         o.reset(); e.reset()
         o.observe(); e.observe()
         assert np.array_equal(o.obs, e.obs) and np.all(o.obs[:, lo:lo + 4] == 0)

@@ -6,27 +6,23 @@ import pytest
 import torch
 
 import contacts_cases as cc
+from backends import Device
 
 pytestmark = pytest.mark.gpu
 
 
 def device_env(cfg, record=True):
-    from hrl_pybullet_envs_amd.vec_env import BatchedEnv
-    g = BatchedEnv(cfg, 'cuda:0')
-    g.reset()
+    d = Device(cfg)
+    d.reset()
     if record:
-        g.record_contacts().fill_(float('nan'))  # every float must be written by the step
-    return g
+        d.env.record_contacts().fill_(float('nan'))  # every float must be written by the step
+    return d
 
 
-def push(g, s):
-    g.state.copy_(torch.tensor(s['state'])); g.items.copy_(torch.tensor(s['items'])); g.aux.copy_(torch.tensor(s['aux']))   # (copies: the trace is read-only)
-
-
-def device_records(tr, g=None):
-    g = g or device_env(tr.cfg)
-    rec = cc.run(tr, g, lambda env, a: env.step(torch.tensor(a).cuda()), fetch=lambda env: env.contacts.cpu().numpy(), push=push)
-    g.close()
+def device_records(tr, step=lambda d, a: d.env.step(torch.tensor(a).cuda())):
+    d = device_env(tr.cfg)
+    rec = cc.run(tr, d, step, fetch=lambda d: d.env.contacts.cpu().numpy(), push=Device.push)
+    d.close()
     return rec
 
 
@@ -57,7 +53,7 @@ def test_device_records_equal_the_oracle_directly():
 def test_off_means_off(name):
     """The same free-running rollout with and without record_contacts(): state, items, aux and every output identical bitwise."""
     tr = cc.trace(name)
-    a_env, b_env = device_env(tr.cfg), device_env(tr.cfg, record=False)
+    a_env, b_env = device_env(tr.cfg).env, device_env(tr.cfg, record=False).env
     for s in tr.steps:
         a = torch.tensor(s['act']).cuda()
         ra, rb = a_env.step(a), b_env.step(a)
@@ -96,19 +92,19 @@ def test_step_host_and_a_graph_replay_write_the_same_record():
     tr = cc.trace('items')
     eager = device_records(tr)
     # step_host(): actions from and outputs to pinned host memory, the report stays in HBM
-    g = device_env(tr.cfg)
-    host = cc.run(tr, g, lambda env, a: env.step_host(a), fetch=lambda env: env.contacts.cpu().numpy(), push=push)
-    g.close()
+    host = device_records(tr, lambda d, a: d.env.step_host(a))
     assert np.array_equal(cc.bits(host), cc.bits(eager))
     # switched on AFTER the host record exists: step_host()'s record follows
-    g = device_env(tr.cfg, record=False)
+    d = device_env(tr.cfg, record=False)
+    g = d.env
     g.step_host(tr.steps[0]['act'])
     g.record_contacts()
-    push(g, tr.steps[12]); g.step_host(tr.steps[12]['act'])
+    d.push(tr.steps[12]); g.step_host(tr.steps[12]['act'])
     assert np.array_equal(cc.bits(g.contacts.cpu().numpy()), cc.bits(eager[12]))
     g.close()
     # one captured step, replayed: the pointer is fixed, the replay writes the same tensor
-    g = device_env(tr.cfg)
+    d = device_env(tr.cfg)
+    g = d.env
     static_a = torch.tensor(tr.steps[0]['act']).cuda()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -119,7 +115,7 @@ def test_step_host_and_a_graph_replay_write_the_same_record():
     with torch.cuda.graph(graph):
         g.step(static_a)
     for t in (10, 11):
-        push(g, tr.steps[t]); static_a.copy_(torch.tensor(tr.steps[t]['act']))
+        d.push(tr.steps[t]); static_a.copy_(torch.tensor(tr.steps[t]['act']))
         g.contacts.fill_(float('nan'))
         graph.replay()
         torch.cuda.synchronize()

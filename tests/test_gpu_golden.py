@@ -8,36 +8,15 @@ import pytest
 import torch
 
 import golden_replay
+from backends import Device
 from hrl_pybullet_envs_amd import _capi as K
 
 pytestmark = pytest.mark.gpu
 
 
-class GpuSide:
-    def __init__(self, cfg):
-        from hrl_pybullet_envs_amd.vec_env import BatchedEnv
-        self.g = BatchedEnv(cfg, 'cuda:0')
-        self.n = cfg.num_envs
-
-    def set(self, qpos, qvel, items=None, aux3=None, initial_z=None):
-        g = self.g
-        if initial_z is not None:
-            g.state[:, K.HRL_INITZ_OFF] = initial_z
-        if items is not None:
-            g.items[:, :items.shape[1]] = torch.from_numpy(items).cuda()
-        if aux3 is not None:
-            g.aux[:, 3] = torch.from_numpy(aux3).cuda()
-        g.set_state(torch.from_numpy(qpos), torch.from_numpy(qvel), observe=False)   # hrl_set_state
-
-    def observe(self):
-        obs = self.g.observe().cpu().numpy().copy()   # hrl_observe
-        self.g.close()
-        return obs
-
-
 def test_reference_fixtures_on_the_device():
     from hrl_pybullet_envs_amd import _lib
-    golden_replay.check(golden_replay.replay_all(GpuSide, _lib.default_config))
+    golden_replay.check(golden_replay.replay_all(Device, _lib.default_config))
 
 
 def test_set_state_returns_the_observation_of_the_new_state():

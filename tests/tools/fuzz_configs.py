@@ -17,6 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import backends as B  # noqa: E402
 import orc  # noqa: E402
 from hrl_pybullet_envs_amd import _capi as K  # noqa: E402
 
@@ -165,67 +166,16 @@ def clone(cfg):
     return K.hrl_config.from_buffer_copy(bytes(cfg))
 
 
-class GpuSide:
+class GpuSide(B.Device):
     def __init__(self, cfg):
-        import torch
-        from hrl_pybullet_envs_amd.vec_env import BatchedEnv
-        self.t, self.g = torch, BatchedEnv(cfg, 'cuda:0')
-        self.g.count_solver_rows()
-
-    def reset(self, mask=None): self.g.reset(None if mask is None else self.t.from_numpy(mask).cuda())
-    def step(self, a): self.g.step(self.t.from_numpy(a).cuda())
-
-    def push(self, o):
-        t, g = self.t, self.g
-        g.state.copy_(t.from_numpy(o.state)); g.items.copy_(t.from_numpy(o.items)); g.aux.copy_(t.from_numpy(o.aux))
-
-    def observe(self, mask): self.g.observe(None if mask is None else self.t.from_numpy(mask).cuda())
-    def set_goals(self, goals, mask): self.g.set_goals(self.t.from_numpy(goals).cuda(), None if mask is None else self.t.from_numpy(mask).cuda())
-    def next_target(self, mask): return self.g.next_target(None if mask is None else self.t.from_numpy(mask).cuda())[1].cpu().numpy()
-
-    def outputs(self):
-        g = self.g
-        d = dict(state=g.state, items=g.items, aux=g.aux, obs=g.obs, rew=g.reward, done=g.done, info=g.info, final_obs=g.final_obs, truncated=g.truncated)
-        if g.cfg.env_kind == K.HRL_ANT_FLAGRUN: d['goal'] = g.goal
-        d['solver_rows'] = g.solver_rows
-        return {k: v.cpu().numpy() for k, v in d.items()}
-
-    def close(self): self.g.close()
+        super().__init__(cfg, count_rows=True)
 
 
-class EmuSide:
+class EmuSide(B.Emu):
     ASAN = bool(os.environ.get('HRL_EMU_ASAN'))   # the AddressSanitizer + UBSan build of the executor (tests/test_emu_asan.py preloads libasan)
 
     def __init__(self, cfg):
-        import emu_env
-        self.e = emu_env.EmuEnv(cfg, asan=self.ASAN)
-        msg = emu_env.lib(self.ASAN).emu_validate(orc.C.byref(cfg))
-        if msg: raise ValueError(msg.decode())
-
-    def reset(self, mask=None): self.e.reset(mask)
-    def step(self, a): self.e.step(a)
-
-    def push(self, o):
-        e = self.e
-        e.state[...] = o.state; e.items[...] = o.items; e.aux[...] = o.aux
-
-    def observe(self, mask): self.e.observe(mask)
-
-    def set_goals(self, goals, mask):
-        import emu_env
-        assert emu_env.lib(self.ASAN).emu_set_goals(orc.C.byref(self.e.cfg), orc.C.byref(self.e._bufs()), orc.ptr(goals), goals.shape[1], orc.ptr(mask), 0) == 0
-
-    def next_target(self, mask):
-        import emu_env
-        ok = np.ones(self.e.N, np.uint8)
-        assert emu_env.lib(self.ASAN).emu_next_target(orc.C.byref(self.e.cfg), orc.C.byref(self.e._bufs()), orc.ptr(mask), orc.ptr(ok), 0) == 0
-        return ok
-
-    def outputs(self):
-        e = self.e
-        return dict(state=e.state, items=e.items, aux=e.aux, obs=e.obs, rew=e.rew, done=e.done, info=e.info, final_obs=e.final_obs, truncated=e.truncated, goal=e.goal, solver_rows=e.solver_rows)
-
-    def close(self): pass
+        super().__init__(cfg, asan=self.ASAN)
 
 
 def run(Side, kind, seed, T):
@@ -242,9 +192,8 @@ def run(Side, kind, seed, T):
     o.reset(); s.reset()
     CLOCK['create'] += time.time() - t0
     ended = 0
-    names = ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info', 'final_obs', 'truncated') + (('goal',) if kind == K.HRL_ANT_FLAGRUN else ()) + ('solver_rows',)
+    names = B.ALL + (('goal',) if kind == K.HRL_ANT_FLAGRUN else ()) + ('solver_rows',)
     manual = kind == K.HRL_ANT_FLAGRUN and cfg.flag_manual_goals and cfg.flag_max_targets >= 1   # goals near the robot ignore the list: hrl_set_goals refuses
-    L = orc.lib()
 
     def some(p=0.5):
         return None if rng.rand() < 0.3 else np.ascontiguousarray(rng.rand(n) < p, np.uint8)
@@ -252,8 +201,7 @@ def run(Side, kind, seed, T):
     def give_goals(mask):
         G = int(rng.randint(1, cfg.flag_goal_capacity + 1))
         goals = rng.uniform(-cfg.flag_size / 2, cfg.flag_size / 2, (n, G, 2)).astype(np.float32)
-        L.orc_set_goals_batch_f32(orc.C.byref(o.cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), orc.ptr(goals), G, orc.ptr(mask), orc.ptr(o.obs))
-        s.set_goals(goals, mask)
+        o.set_goals(goals, mask); s.set_goals(goals, mask)
 
     if manual: give_goals(None)
     for t in range(-1, T):
@@ -298,9 +246,8 @@ def run(Side, kind, seed, T):
             o.reset(m); s.reset(m)
         if what == 2 and manual: give_goals(some())
         if what == 3 and kind == K.HRL_ANT_FLAGRUN:
-            m, ok = some(), np.ones(n, np.uint8)
-            L.orc_next_target_batch_f32(orc.C.byref(o.cfg), orc.ptr(o.state), orc.ptr(o.items), orc.ptr(o.aux), orc.ptr(m), orc.ptr(o.obs), orc.ptr(ok))
-            if not np.array_equal(ok, s.next_target(m)):
+            m = some()
+            if not np.array_equal(o.next_target(m), s.next_target(m)):
                 s.close()
                 return f'kind {kind} seed {seed} step {t}: next_target ok flags differ; config {kw}', ended
         if t >= 0:
@@ -313,16 +260,16 @@ def run(Side, kind, seed, T):
             CLOCK['side steps'] += t1 - t0; CLOCK['oracle steps'] += t2 - t1
             ended += int(o.done.sum())
         t0 = time.time()
-        out = s.outputs()
+        out = {name: getattr(s, name) for name in (names if t >= 0 else ('state', 'items', 'aux', 'obs'))}
         CLOCK['read back'] += time.time() - t0
-        for name in names if t >= 0 else ('state', 'items', 'aux', 'obs'):
-            A, B = getattr(o, name).reshape(n, -1), out[name].reshape(n, -1)
-            ok = (A == B) | ((A != A) & (B != B))
+        for name in out:
+            A, G = getattr(o, name).reshape(n, -1), out[name].reshape(n, -1)
+            ok = (A == G) | ((A != A) & (G != G))
             if not ok.all():
                 e = int(np.where(~ok.all(1))[0][0])
                 s.close()
                 return (f'kind {kind} seed {seed} step {t}: {name} differs for env {e} at {np.where(~ok[e])[0][:8]}; oracle {A[e][~ok[e]][:6]} '
-                        f'other {B[e][~ok[e]][:6]}; config {kw}'), ended
+                        f'other {G[e][~ok[e]][:6]}; config {kw}'), ended
     s.close()
     return None, ended
 

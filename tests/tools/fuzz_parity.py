@@ -10,6 +10,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import backends as B  # noqa: E402
 import orc  # noqa: E402
 from hrl_pybullet_envs_amd import _capi as K  # noqa: E402
 
@@ -17,41 +18,14 @@ KINDS = [K.HRL_ANT_FLAT, K.HRL_ANT_GATHER, K.HRL_ANT_MAZE, K.HRL_POINT_GATHER, K
 VALS = [np.nan, np.inf, -np.inf, 1e20, -1e20, 3e38, -3e38, 1e-40, -1e-40, -0.0, 0.0, 1e-20, 1e10, 5.0, -5.0, 100.0]
 
 
-class GpuSide:
+class GpuSide(B.Device):
     def __init__(self, kind, n, seed, auto_reset, kw):
-        import torch
-        from hrl_pybullet_envs_amd import _lib
-        from hrl_pybullet_envs_amd.vec_env import BatchedEnv
-        self.t, self.g = torch, BatchedEnv(_lib.default_config(kind, num_envs=n, seed=seed, auto_reset=auto_reset, **kw), 'cuda:0')
-
-    def reset(self): self.g.reset()
-
-    def step(self, o, a):  # the oracle's (edited) pre-step buffers are pushed, then both step
-        t, g = self.t, self.g
-        g.state.copy_(t.from_numpy(o.state)); g.items.copy_(t.from_numpy(o.items)); g.aux.copy_(t.from_numpy(o.aux))
-        g.step(t.from_numpy(a).cuda())
-
-    def outputs(self):
-        g = self.g
-        return {k: v.cpu().numpy() for k, v in dict(state=g.state, items=g.items, aux=g.aux, obs=g.obs, rew=g.reward, done=g.done, info=g.info,
-                                                     final_obs=g.final_obs, truncated=g.truncated).items()}
+        super().__init__(B.Device.config(kind, num_envs=n, seed=seed, auto_reset=auto_reset, **kw))
 
 
-class EmuSide:
+class EmuSide(B.Emu):
     def __init__(self, kind, n, seed, auto_reset, kw):
-        import emu_env
-        self.e = emu_env.EmuEnv(orc.default_config(kind, num_envs=n, seed=seed, auto_reset=auto_reset, **kw))
-
-    def reset(self): self.e.reset()
-
-    def step(self, o, a):
-        e = self.e
-        e.state[...] = o.state; e.items[...] = o.items; e.aux[...] = o.aux
-        e.step(a)
-
-    def outputs(self):
-        e = self.e
-        return dict(state=e.state, items=e.items, aux=e.aux, obs=e.obs, rew=e.rew, done=e.done, info=e.info, final_obs=e.final_obs, truncated=e.truncated)
+        super().__init__(orc.default_config(kind, num_envs=n, seed=seed, auto_reset=auto_reset, **kw))
 
 
 def run(Side, kind, seed, auto_reset, n=48, T=10, kw=None):
@@ -78,14 +52,13 @@ def run(Side, kind, seed, auto_reset, n=48, T=10, kw=None):
                 elif what == 2 and kind in (K.HRL_ANT_GATHER, K.HRL_POINT_GATHER): o.items[r, rng.randint(0, o.items.shape[1])] = v
                 else: a[r, rng.randint(0, o.ad)] = v
         pre = o.state.copy()
-        s.step(o, a); o.step(a)
-        out = s.outputs()
-        for name in ('state', 'items', 'aux', 'obs', 'rew', 'done', 'info', 'final_obs', 'truncated'):
-            A, B = getattr(o, name).reshape(n, -1), out[name].reshape(n, -1)
-            ok = (A == B) | ((A != A) & (B != B))
+        s.push(o); s.step(a); o.step(a)  # the oracle's (edited) pre-step buffers are pushed, then both step
+        for name in B.ALL:
+            A, G = getattr(o, name).reshape(n, -1), getattr(s, name).reshape(n, -1)
+            ok = (A == G) | ((A != A) & (G != G))
             if not ok.all():
                 e = int(np.where(~ok.all(1))[0][0])
-                return f'kind {kind} {kw} seed {seed} auto_reset {auto_reset} step {t}: {name} differs for env {e} at {np.where(~ok[e])[0][:8]}; oracle {A[e][~ok[e]][:6]} other {B[e][~ok[e]][:6]}; pre-step state {pre[e, :29]}'
+                return f'kind {kind} {kw} seed {seed} auto_reset {auto_reset} step {t}: {name} differs for env {e} at {np.where(~ok[e])[0][:8]}; oracle {A[e][~ok[e]][:6]} other {G[e][~ok[e]][:6]}; pre-step state {pre[e, :29]}'
     return None
 
 

@@ -10,22 +10,21 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import orc  # noqa: E402
-from hrl_pybullet_envs_amd import _lib  # noqa: E402
-from hrl_pybullet_envs_amd.vec_env import BatchedEnv  # noqa: E402
+from backends import Device  # noqa: E402
 
 
 def main():
     kind = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 256
     T = int(sys.argv[3]) if len(sys.argv) > 3 else 100
-    cfg = _lib.default_config(kind, num_envs=n, seed=3, auto_reset=1)
-    g = BatchedEnv(cfg, 'cuda:0'); o = orc.OracleEnv(orc.default_config(kind, num_envs=n, seed=3, auto_reset=1), np.float32)
+    d = Device(Device.config(kind, num_envs=n, seed=3, auto_reset=1)); o = orc.OracleEnv(orc.default_config(kind, num_envs=n, seed=3, auto_reset=1), np.float32)
+    g = d.env
     g.reset(); o.reset()
     rng = np.random.RandomState(0)
     es, eo, flips = [], [], 0
     for t in range(T):
         a = rng.uniform(-1, 1, (n, o.ad)).astype(np.float32)
-        g.state.copy_(torch.from_numpy(o.state)); g.items.copy_(torch.from_numpy(o.items)); g.aux.copy_(torch.from_numpy(o.aux))
+        d.push(o)
         go, gr, gd, gi = g.step(torch.from_numpy(a).cuda()); o.step(a)
         torch.cuda.synchronize()
         flip = (gd.cpu().numpy() != o.done) | (gr.cpu().numpy() != o.rew)

@@ -12,8 +12,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import orc  # noqa: E402
-from hrl_pybullet_envs_amd import _lib  # noqa: E402
-from hrl_pybullet_envs_amd.vec_env import BatchedEnv  # noqa: E402
+from backends import Device  # noqa: E402
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 2100
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
@@ -25,7 +24,7 @@ for k in sys.argv[3:]:  # named config sets after the kinds: `big` (32 items, 24
     kw.update(KW.get(k, {}))
 names = ['flat', 'gather', 'maze', 'point', 'maze_mj', 'flagrun']
 for kind in kinds:
-    g = BatchedEnv(_lib.default_config(kind, num_envs=n, seed=5, auto_reset=1, **kw), 'cuda:0')
+    g = Device(Device.config(kind, num_envs=n, seed=5, auto_reset=1, **kw)).env
     o = orc.OracleEnv(orc.default_config(kind, num_envs=n, seed=5, auto_reset=1, **kw), np.float32)
     g.reset(); o.reset()
     rng = np.random.RandomState(kind)
