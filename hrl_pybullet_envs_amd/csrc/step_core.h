@@ -2363,7 +2363,15 @@ HRL_DEV void write_contacts(X &x, const DevCfg &c, float *rec, const float *q0, 
         } else {
             const int m = lane - 4, i = m / 5, w = m - 5 * i; /* i < 12 */
             if (i < n_contacts) {
-                if (w == 0) { v0 = L.cr[i][0] + q0[0]; v1 = L.cr[i][1] + q0[1]; v2 = L.cr[i][2] + q0[2]; v3 = L.cdist_[i]; }
+                if (w == 0) {
+                    v0 = L.cr[i][0] + q0[0]; v1 = L.cr[i][1] + q0[1]; v2 = L.cr[i][2] + q0[2]; v3 = L.cdist_[i];
+                    if (KIND != 3 && L.clink2[i] >= 0) { /* a self contact: the solver's point is midway between the two surfaces (capsule_pair); reported,
+                                                            as for every other contact, is the point on the surface of `link` -- half the signed distance
+                                                            further along the normal, which points from link2 to link */
+                        const float half = 0.5f * v3;
+                        v0 = fma_(half, L.cdir[0][i][0], v0); v1 = fma_(half, L.cdir[0][i][1], v1); v2 = fma_(half, L.cdir[0][i][2], v2);
+                    }
+                }
                 else if (w < 4) {
                     const int d = w - 1;
                     v0 = L.cdir[d][i][0]; v1 = L.cdir[d][i][1]; v2 = L.cdir[d][i][2];

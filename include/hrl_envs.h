@@ -247,7 +247,8 @@ typedef struct hrl_buffers_ext {
      *            [12] bit mask of the joints that hold a limit row  [13] of those whose row has sign -1  [14..15] 0
      *   contact i < n_contacts, in the solver's contact order, at float HRL_CONTACTS_HEADER + HRL_CONTACT_WIDTH * i:
      *            +0..2 world position (the point relative to the torso / body origin + that origin as the collision pass saw it: the pose at the
-     *                  start of the step's last substep)                                   +3  signed distance
+     *                  start of the step's last substep): the point on the ROBOT's surface -- of `link`, also in a self contact, where the
+     *                  second body's point is position - distance x normal             +3  signed distance to the other surface
      *            +4..6 normal (towards the robot body; self contacts: towards the first body) +7  lambda normal
      *            +8..10 tangent 1   +11 lambda t1     +12..14 tangent 2   +15 lambda t2
      *            +16 surface code (HRL_SURF_*)  +17 link (level | leg << 2; 0 for the point bot)  +18 link2 (-1 unless a self contact)

@@ -156,3 +156,47 @@ def test_single_env_get_contact_points():
     up = contacts.link_force(d)[:, :, 2].sum(1)   # ground contacts push up or, still closing within the contact distance, not at all
     assert bool((up >= 0).all()) and int((up > 0).sum()) >= 4
     env.close()
+
+
+# ------------------------------------------------------------------------------------------------ the device's records against fp64 physics
+# The checks of tests/test_contacts_physics.py (helpers: tests/contacts_cases.py) on the kernel's own records and the kernel's own states
+# after the step, at one substep per step (the balance is stated for frame_skip = 1 only: with four substeps the pose at the start of the
+# last one is no output).  Envs that ended in a step are left out here: their state was reset.
+def device_run(name, n=None):
+    """(trace, records [steps, N, 256], states after each step [steps, N, stride]) of the scenario at one substep per step on the device"""
+    tr = cc.trace(name, n, 1)
+    d = device_env(tr.cfg)
+    after = []
+    rec = cc.run(tr, d, lambda d, a: d.env.step(torch.tensor(a).cuda()), fetch=lambda d: d.env.contacts.cpu().numpy(), push=Device.push, after=after)
+    d.close()
+    assert not np.isnan(rec).any()
+    return tr, rec, np.stack(after)
+
+
+@pytest.mark.parametrize('name,n', [(name, None) for name in cc.NAMES] + [('items', 5), ('self', 5)])
+def test_device_records_against_fp64_physics(name, n):
+    """The kernel's records and after-states: the momentum balance (tolerances, clamp criterion and coverage floors of
+    tests/test_contacts_physics.py; the floors hold for the full scenario shapes), the geometry of every contact against fp64 kinematics,
+    and contacts.link_force on CUDA tensors against the numpy regrouping of the records.  n = 5: a ragged last group."""
+    tr, rec, after = device_run(name, n)
+    b = cc.balance(tr, rec, after, skip_done=True)
+    cc.check_balance(name, b, floors=n is None)   # (the floors are the full shapes')
+    if name != 'point':
+        g = cc.geometry(tr, rec, skip_done=True)
+        print(name, n, g)
+        assert n is not None or cc.geometry_floor(name, g), (name, g)
+    worst, n_self = cc.check_link_force(rec.reshape(-1, cc.STRIDE), cc.P_TOL, device='cuda')
+    print(f'{name} {n}: link_force on the device vs numpy, worst {worst:.2e} N s; {n_self} self contacts')
+
+
+def test_device_capsule_records_against_fp64_physics():
+    """The same on the states of tests/capsule_cases.py: mid-section and second-support contacts among the compared env-steps."""
+    mid = second = 0
+    for name in cc.CAPSULE:
+        tr, rec, after = device_run(name)
+        b = cc.balance(tr, rec, after, skip_done=True)
+        cc.check_balance(name, b, clamp_share=1.0)
+        m, s = cc.capsule_coverage(tr, lambda t: [i for tt, i in b['rows'] if tt == t])
+        mid += m; second += s
+        print(name, cc.geometry(tr, rec, skip_done=True))
+    assert mid >= 1 and second >= 1, (mid, second)

@@ -102,6 +102,13 @@ def ant_dynamics(p, q, u, tau):
     return M, b, ud
 
 
+def ant_points(p, q):
+    """([leg][hip point, ankle point, foot tip][xyz], [body][xyz] centres of mass) of pose q in world coordinates"""
+    legs, coms = np.zeros(36), np.zeros(27)
+    lib().tb_ant_points(C.byref(p), _p(np.ascontiguousarray(q, np.float64)), _p(legs), _p(coms))
+    return legs.reshape(4, 3, 3), coms.reshape(9, 3)
+
+
 def ant_energy_momentum(p, q, u):
     o = np.zeros(8)
     lib().tb_ant_energy_momentum(C.byref(p), _p(np.ascontiguousarray(q, np.float64)), _p(np.ascontiguousarray(u, np.float64)), _p(o))
