@@ -202,6 +202,11 @@ class BatchedGymEnv:
         render_device.default_view for other views).  `render(mode='rgb_array')` stays the host-drawn picture of one env."""
         return self._backend().render(view, mask, out)
 
+    def scan_batch(self, spec=None, mask=None, out=None):
+        """A ring of range rays for EVERY env in one launch: (range float32, hit int32), each [N, n_rays] on the env's device
+        (BatchedEnv.scan; scan_device.default_spec / sensor_spec for other rings)."""
+        return self._backend().scan(spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

@@ -163,6 +163,32 @@ class BatchedEnv:
         self._last_render_mask = m  # keep alive until the stream has consumed it
         return out
 
+    def scan(self, spec=None, mask=None, out=None):
+        """A ring of range rays per env: (range float32 [N, n_rays] in metres, hit int32 [N, n_rays]) on this device, from ONE launch on the
+        current stream (scan_device.py, include/hrl_scan.h).  The rays see the walls, the maze box, food, poison and the target as finite
+        shapes; `hit` = class code | index << 8 (scan_device.decode).  `spec`: an hrl_scan_spec (scan_device.default_spec(cfg, frame,
+        n_rays), scan_device.sensor_spec(...)); None = 64 rays around the robot's heading out to the arena's diagonal.  Envs with
+        mask[i] == 0 keep what `out` holds (zeros in fresh tensors).  `out=(range, hit)` is reused when given.  The scan is of the state /
+        items / aux tensors as they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import scan_device as S
+        if spec is None:
+            spec = getattr(self, '_default_scan', None)
+            if spec is None:
+                spec = self._default_scan = S.default_spec(self.cfg)
+        if out is None:
+            if not 1 <= spec.n_rays <= S.MAX_RAYS:   # (the library refuses it too; no tensor can be shaped after it)
+                raise ValueError(f'spec.n_rays must be within 1..{S.MAX_RAYS}, got {spec.n_rays}')
+            make = torch.empty if mask is None else torch.zeros
+            rng = make(self.num_envs, spec.n_rays, dtype=torch.float32, device=self.device)
+            hit = make(self.num_envs, spec.n_rays, dtype=torch.int32, device=self.device)
+        else:
+            rng, hit = S.check_out(out, self.num_envs, spec, self.device)
+        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            S.scan(self.cfg, self._bufs_ref, spec, None if m is None else m.data_ptr(), rng, hit, self._stream())
+        self._last_scan_mask = m  # keep alive until the stream has consumed it
+        return rng, hit
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)

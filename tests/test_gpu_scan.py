@@ -1,0 +1,201 @@
+"""The batched range scanner on the MI355X (csrc/scan_hip.hip, include/hrl_scan.h) against the host build of its specification
+(tests/scan_host, csrc/scan_core.h), bit for bit, and its surface: masks, streams and graph replay, `out=`, the gym classes'
+scan_batch(), and that the step does not notice it.  At most 16 envs per test."""
+import numpy as np
+import pytest
+import torch
+
+import scan_cases as sc
+from hrl_pybullet_envs_amd import _capi as K
+from hrl_pybullet_envs_amd import scan_device as S
+from test_gpu_render import host_items, make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
+
+pytestmark = pytest.mark.gpu
+N = 5
+
+
+def bits(pair):
+    r, h = pair
+    r, h = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (r, h))
+    assert r.dtype == np.float32 and h.dtype == np.int32
+    return r.view(np.uint32), h
+
+
+def same(a, b):
+    (ra, ha), (rb, hb) = bits(a), bits(b)
+    return np.array_equal(ra, rb) and np.array_equal(ha, hb)
+
+
+def both(env, st, it, aux, spec):
+    """(device scan, host-build scan) of the records st / it / aux, written into the env's tensors first."""
+    put(env, st, it, aux)
+    return env.scan(spec), sc.scan_host(env.cfg, st, host_items(env, it), aux, spec)
+
+
+@pytest.mark.parametrize('kind', sc.KINDS)
+def test_device_scan_equals_the_host_build_bit_for_bit(kind):
+    """Six kinds x two frames x 1, 37, 64, 65 and 512 rays x max_range 6 and 20 at N = 5, on the states of 30 steps, on the hand-made
+    poses (through set_state) and on the hostile states: `range` as uint32 and `hit` equal the host build of scan_core.h."""
+    env, st, it, aux = stepped(kind)
+    try:
+        for spec in sc.all_specs():
+            dev, host = both(env, st, it, aux, spec)
+            assert tuple(dev[0].shape) == tuple(dev[1].shape) == (N, spec.n_rays) and dev[0].dtype == torch.float32 and dev[1].dtype == torch.int32
+            assert same(dev, host), (kind, spec.n_rays, spec.frame, spec.max_range)
+        hm = sc.hand_made(env.cfg, st)
+        put(env, st, it, aux)
+        env.set_state(torch.from_numpy(hm[:, :15].copy()), torch.from_numpy(hm[:, 15:29].copy()))
+        torch.cuda.synchronize()
+        got = env.state.cpu().numpy()
+        assert np.array_equal(got[:, :15], hm[:, :15])
+        for frame in sc.FRAMES:
+            for n in (65, 512):
+                spec = sc.spec_of(n, frame, 20.0)
+                assert same(env.scan(spec), sc.scan_host(env.cfg, got, host_items(env, it), aux, spec)), (kind, frame, n, 'hand-made')
+        for s, i2, a, _, _, _, _, _ in sc.hostile(env.cfg, st, it, aux):
+            for frame in sc.FRAMES:
+                spec = sc.spec_of(65, frame, 20.0)
+                dev, host = both(env, s, i2, a, spec)
+                assert same(dev, host), (kind, frame, 'hostile')
+    finally:
+        put(env, st, it, aux)
+
+
+def test_class_subsets_and_the_default_spec():
+    env, st, it, aux = stepped(K.HRL_ANT_GATHER)
+    for classes in (S.WALL, S.FOOD, S.POISON, S.FOOD | S.POISON, S.WALL | S.TARGET | S.BOX):
+        spec = sc.spec_of(37, S.HRL_SCAN_HEADING, 20.0, classes)
+        dev, host = both(env, st, it, aux, spec)
+        assert same(dev, host), classes
+    rng, hit = env.scan()   # 64 rays around the heading, all classes, out to the arena's diagonal
+    assert tuple(rng.shape) == (N, 64) and rng.device == env.device and hit.device == env.device
+    assert same((rng, hit), sc.scan_host(env.cfg, st, it, aux, S.default_spec(env.cfg)))
+    cls, idx = S.decode(hit)
+    assert int(cls.max()) <= S.HIT_TARGET and bool((cls != 0).any()) and bool((rng[cls == 0] == S.default_spec(env.cfg).max_range).all())
+
+
+def test_masked_envs_are_untouched():
+    env = make_env(K.HRL_ANT_MAZE, n=7)
+    env.reset()
+    spec = sc.spec_of(65, S.HRL_SCAN_HEADING, 20.0)
+    full = bits(env.scan(spec))
+    mask = torch.tensor([1, 0, 1, 0, 1, 0, 1], dtype=torch.uint8)
+    out = torch.full((7, 65), -7.0, device='cuda'), torch.full((7, 65), -7, dtype=torch.int32, device='cuda')
+    got = env.scan(spec, mask=mask, out=out)
+    assert got[0] is out[0] and got[1] is out[1]
+    r, h = bits(out)
+    for e in range(7):
+        if mask[e]:
+            assert np.array_equal(r[e], full[0][e]) and np.array_equal(h[e], full[1][e])
+        else:
+            assert (out[0][e] == -7).all() and (h[e] == -7).all()
+    fresh = bits(env.scan(spec, mask=mask))
+    assert (fresh[0][1] == 0).all() and (fresh[1][1] == 0).all() and np.array_equal(fresh[0][0], full[0][0])
+    env.close()
+
+
+def test_scan_follows_the_stream_and_replays_in_a_graph():
+    """step + scan captured once (the first scan call ran before the capture) and replayed three times give the scans of the eager
+    sequence; the launch goes to the env's current stream."""
+    kind, n = K.HRL_ANT_GATHER, 16
+    spec = sc.spec_of(65, S.HRL_SCAN_HEADING, 20.0)
+    acts = torch.rand(4, n, 8, device='cuda', generator=torch.Generator(device='cuda').manual_seed(5)) * 2 - 1
+    eager, eager_scans = make_env(kind, n), []
+    eager.reset()
+    for r in range(4):
+        eager.step(acts[r])
+        eager_scans.append(tuple(x.clone() for x in eager.scan(spec)))
+    env = make_env(kind, n)
+    env.reset()
+    static_a = acts[0].clone()
+    out = torch.zeros(n, 65, device='cuda'), torch.zeros(n, 65, dtype=torch.int32, device='cuda')
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):   # the warm-up torch asks for; the scan's constants are uploaded here, outside the capture
+        env.step(static_a)
+        env.scan(spec, out=out)
+        first = tuple(x.clone() for x in out)
+    torch.cuda.current_stream().wait_stream(side)
+    assert same(first, eager_scans[0])
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        env.step(static_a)
+        env.scan(spec, out=out)
+    for r in range(1, 4):
+        static_a.copy_(acts[r])
+        g.replay()
+        assert same(out, eager_scans[r]), r
+    torch.cuda.synchronize()
+    assert torch.equal(env.state, eager.state)
+    del g
+    env.close(); eager.close()
+
+
+def test_out_is_reused_and_checked():
+    env, st, it, aux = stepped(K.HRL_POINT_GATHER)
+    put(env, st, it, aux)
+    spec = sc.spec_of(37, S.HRL_SCAN_WORLD, 6.0)
+    out = torch.zeros(N, 37, device='cuda'), torch.zeros(N, 37, dtype=torch.int32, device='cuda')
+    p = out[0].data_ptr(), out[1].data_ptr()
+    got = env.scan(spec, out=out)
+    assert got[0] is out[0] and got[1] is out[1] and (got[0].data_ptr(), got[1].data_ptr()) == p
+    assert same(out, sc.scan_host(env.cfg, st, it, aux, spec))
+    with pytest.raises(TypeError):
+        env.scan(spec, out=(out[0], out[1].float()))
+    with pytest.raises(TypeError):
+        env.scan(spec, out=(out[0].int(), out[1]))
+    with pytest.raises(TypeError):
+        env.scan(spec, out=out[0])
+    with pytest.raises(ValueError):
+        env.scan(spec, out=(torch.zeros(N, 64, device='cuda'), out[1]))
+    with pytest.raises(ValueError):
+        env.scan(spec, out=(out[0], torch.zeros(N, 37, dtype=torch.int32)))
+
+
+def test_scan_batch_of_a_gym_class_equals_the_batched_env():
+    import hrl_pybullet_envs_amd as H
+    env = H.AntGatherBulletEnv(num_envs=5, device='cuda:0', seed=3)
+    env.reset()
+    for _ in range(3):
+        env.step(torch.zeros(5, 8, device='cuda'))
+    b = env._backend()
+    spec = S.default_spec(b.cfg, 'world', 37)
+    a, c = env.scan_batch(spec), b.scan(spec)
+    assert a[0].dtype == torch.float32 and a[1].dtype == torch.int32 and tuple(a[0].shape) == tuple(a[1].shape) == (5, 37) and same(a, c)
+    assert same(a, sc.scan_host(b.cfg, b.state.cpu().numpy(), b.items.cpu().numpy(), b.aux.cpu().numpy(), spec))
+    env.close()
+
+
+def test_the_step_does_not_notice_the_scanner():
+    """20 steps of a 16-env gather shard with scan calls interleaved are bit-identical to the same steps without them."""
+    kind, n = K.HRL_ANT_GATHER, 16
+    a, b = make_env(kind, n), make_env(kind, n)
+    a.reset(); b.reset()
+    acts = torch.rand(20, n, 8, device='cuda', generator=torch.Generator(device='cuda').manual_seed(9)) * 2 - 1
+    specs = [sc.spec_of(r, f, 20.0) for r in (37, 512) for f in sc.FRAMES]
+    for t in range(20):
+        oa = [x.clone() for x in a.step(acts[t])[:3]]
+        b.scan(specs[t % len(specs)])
+        ob = [x.clone() for x in b.step(acts[t])[:3]]
+        b.scan(specs[(t + 1) % len(specs)])
+        for x, y in zip(oa, ob):
+            assert torch.equal(x.view(torch.uint8), y.view(torch.uint8)), t
+    for name in ('state', 'items', 'aux'):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize('field,value', [('n_rays', 0), ('n_rays', 513), ('max_range', float('nan')), ('max_range', 0.0), ('max_range', float('inf')), ('classes', 0),
+                                         ('classes', 32), ('frame', 2), ('first_angle', 65.0), ('struct_size', 16)])
+def test_bad_specs_are_refused_by_the_library(field, value):
+    from hrl_pybullet_envs_amd._lib import HrlError
+    env, st, it, aux = stepped(K.HRL_ANT_FLAT)
+    spec = sc.spec_of(37, S.HRL_SCAN_WORLD, 6.0)
+    setattr(spec, field, value)
+    out = torch.full((N, 600), -7.0, device='cuda'), torch.full((N, 600), -7, dtype=torch.int32, device='cuda')
+    with pytest.raises(HrlError) as e:
+        S.scan(env.cfg, env._bufs_ref, spec, None, out[0], out[1], None)
+    want = sc.scan_host(env.cfg, st, None, aux, spec, out=(np.zeros((N, 600), np.float32), np.zeros((N, 600), np.int32)), expect_ok=False)
+    assert want[0] == K.HRL_ERR_BAD_ARG and want[1] in str(e.value)
+    torch.cuda.synchronize()
+    assert bool((out[0] == -7).all()) and bool((out[1] == -7).all())
