@@ -1,6 +1,7 @@
 """Build the gfx950 HIP libraries in-tree: hrl_pybullet_envs_amd/libhrl_envs_hip.so (the step, include/hrl_envs.h),
-hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h) and hrl_pybullet_envs_amd/libhrl_scan_hip.so
-(the batched range scanner, include/hrl_scan.h).
+hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h), hrl_pybullet_envs_amd/libhrl_scan_hip.so
+(the batched range scanner, include/hrl_scan.h) and hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
+include/hrl_probe.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -16,6 +17,8 @@ RENDER_LIB = os.path.join(PKG, 'libhrl_render_hip.so')
 RENDER_SOURCES = ['render_hip.hip', 'render_core.h', 'step_core.h', 'host_cfg.h']   # a library of its own: the step library's code object stays what it was
 SCAN_LIB = os.path.join(PKG, 'libhrl_scan_hip.so')
 SCAN_SOURCES = ['scan_hip.hip', 'scan_core.h', 'render_core.h', 'step_core.h', 'host_cfg.h']   # likewise: it reads the renderer's table, not its library
+PROBE_LIB = os.path.join(PKG, 'libhrl_probe_hip.so')
+PROBE_SOURCES = ['probe_hip.hip', 'probe_core.h', 'scan_core.h', 'render_core.h', 'step_core.h', 'host_cfg.h']   # likewise: the scanner's intersections through an include
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -61,12 +64,19 @@ def build_scan(force=False, verbose=False):
     return _compile(SCAN_LIB, 'scan_hip.hip', verbose)
 
 
+def build_probe(force=False, verbose=False):
+    if not force and not _stale(PROBE_LIB, PROBE_SOURCES, ('hrl_envs.h', 'hrl_render.h', 'hrl_scan.h', 'hrl_probe.h')):
+        return PROBE_LIB
+    return _compile(PROBE_LIB, 'probe_hip.hip', verbose)
+
+
 def build(force=False, verbose=False):
-    """The three libraries; returns the step library's path."""
+    """The four libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     build_render(force, verbose)
     build_scan(force, verbose)
+    build_probe(force, verbose)
     return LIB
 
 
@@ -74,3 +84,4 @@ if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
     print(RENDER_LIB)
     print(SCAN_LIB)
+    print(PROBE_LIB)

@@ -207,6 +207,11 @@ class BatchedGymEnv:
         (BatchedEnv.scan; scan_device.default_spec / sensor_spec for other rings)."""
         return self._backend().scan(spec, mask, out)
 
+    def probe_batch(self, points, spec=None, mask=None, out=None):
+        """Point probes for EVERY env in one launch: Probe(clearance, nearest, sight, blocker, path, via), each [N, P] on the env's
+        device, for `points` float32 [N, P, 2] (BatchedEnv.probe; probe_device.default_spec for other frames and margins)."""
+        return self._backend().probe(points, spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

@@ -1,0 +1,139 @@
+"""The batched point probes (include/hrl_probe.h): loader of libhrl_probe_hip.so, the ctypes mirrors of `hrl_probe_spec` and
+`hrl_probe_out`, and the launch behind `BatchedEnv.probe()` -- for P query points per env of a shard: clearance / nearest, sight /
+blocker and path / via, each [N, P] in HBM, from one kernel launch.
+
+Like the renderer's and the scanner's, the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a
+missing library is an error."""
+import collections
+import ctypes as C
+import os
+
+import torch
+
+from . import _capi as K
+from ._lib import HrlError
+from .scan_device import ALL, BOX, FOOD, HIT_BOX, HIT_FOOD, HIT_NAMES, HIT_NONE, HIT_POISON, HIT_TARGET, HIT_WALL, POISON, TARGET, WALL, decode  # noqa: F401  (the scanner's classes and codes)
+
+HRL_PROBE_WORLD, HRL_PROBE_EGO, HRL_PROBE_HEADING = 0, 1, 2
+FRAMES = {'world': HRL_PROBE_WORLD, 'ego': HRL_PROBE_EGO, 'heading': HRL_PROBE_HEADING}
+MAX_POINTS = 512
+MAX_MARGIN = 2.0
+SKIN = 1e-3
+VIA_NONE, VIA_STRAIGHT, VIA_CORNER0 = 0, 1, 2                                    # `via`: 2 + k = the route first turns at corner k
+
+Probe = collections.namedtuple('Probe', 'clearance nearest sight blocker path via')
+Probe.__new__.__defaults__ = (None,) * 6
+FIELDS = (('clearance', torch.float32), ('nearest', torch.int32), ('sight', torch.float32), ('blocker', torch.int32), ('path', torch.float32), ('via', torch.int32))
+
+_PKG = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get('HRL_PROBE_LIB') or os.path.join(_PKG, 'libhrl_probe_hip.so')
+SYMBOLS = ['hrl_probe_default_spec', 'hrl_probe', 'hrl_probe_last_error']   # every symbol include/hrl_probe.h declares
+_lib = None
+
+
+class hrl_probe_spec(C.Structure):
+    _fields_ = [('struct_size', C.c_uint64), ('n_points', C.c_int32), ('frame', C.c_int32), ('classes', C.c_uint32), ('margin', C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        if 'struct_size' not in kw:
+            self.struct_size = C.sizeof(type(self))
+
+    def copy(self):
+        s = hrl_probe_spec()
+        C.memmove(C.byref(s), C.byref(self), C.sizeof(hrl_probe_spec))
+        return s
+
+
+class hrl_probe_out(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise HrlError(f'{LIB_PATH} is missing: build it with `python -m hrl_pybullet_envs_amd.build` '
+                           '(hipcc --offload-arch=gfx950); the batched point probes have no CPU fallback')
+        L = C.CDLL(LIB_PATH)
+        for s in SYMBOLS:
+            getattr(L, s)
+        L.hrl_probe_last_error.restype = C.c_char_p
+        L.hrl_probe_default_spec.argtypes = [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_probe_spec)]
+        L.hrl_probe.argtypes = [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_probe_spec), C.c_void_p, C.c_void_p, C.POINTER(hrl_probe_out), C.c_void_p]
+        _lib = L
+    return _lib
+
+
+def check(rc):
+    if rc != K.HRL_OK:
+        raise HrlError(f'hrl_probe error {rc}: {lib().hrl_probe_last_error().decode()}')
+
+
+def _frame(frame):
+    if isinstance(frame, str):
+        if frame not in FRAMES:
+            raise ValueError(f'probe frame {frame!r}: one of {sorted(FRAMES)}')
+        return FRAMES[frame]
+    return int(frame)
+
+
+def default_spec(cfg, frame='world', n_points=64):
+    """The library's default probe of `cfg`'s kind (hrl_probe_default_spec: all classes, margin = the torso's radius, the cube's half
+    side for the point bot) for `n_points` points per env in `frame` ('world', 'ego' or 'heading')."""
+    s = hrl_probe_spec()
+    check(lib().hrl_probe_default_spec(C.byref(cfg), _frame(frame), C.byref(s)))
+    s.n_points = int(n_points)
+    return s
+
+
+def corner_table(cfg, margin):
+    """The waypoints `via` indexes, float64 [6, 2] in world coordinates: rows 2 + k are corner k = (+x, +y), (-x, +y), (-x, -y), (+x, -y)
+    of the maze box grown by margin + SKIN; rows 0 (unreachable) and 1 (straight) are NaN, and so is every row of a kind without a box.
+    (A corner beyond the shrunk arena is listed too; no route turns there.)"""
+    t = torch.full((6, 2), float('nan'), dtype=torch.float64)
+    if cfg.env_kind in (K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ):
+        (cx, cy), (hx, hy) = (-2.0, 0.0), (3.0, 2.0)   # host_cfg.h build_devcfg: box (-5, -2) .. (1, 2) (box.xml, maze_scene.py)
+        e = float(margin) + SKIN
+        for k, (sx, sy) in enumerate(((1, 1), (-1, 1), (-1, -1), (1, -1))):
+            t[2 + k, 0], t[2 + k, 1] = cx + sx * (hx + e), cy + sy * (hy + e)
+    return t
+
+
+def probe(cfg, bufs_ref, spec, points, mask_ptr, out, stream):
+    """One launch: the tensors of `out` (a Probe; None fields are not computed), each [N, n_points] on the current device, from the
+    buffer record behind `bufs_ref` and `points` float32 [N, n_points, 2]."""
+    o = hrl_probe_out(**{name: (None if t is None else t.data_ptr()) for (name, _), t in zip(FIELDS, out)})
+    check(lib().hrl_probe(C.byref(cfg), bufs_ref, C.byref(spec), points.data_ptr(), mask_ptr, C.byref(o), stream))
+    return out
+
+
+def check_points(points, n, device):
+    """`points` of BatchedEnv.probe(): float32, contiguous [N, P, 2] with 1 <= P <= 512, on the env's device."""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
+        raise TypeError(f'points must be a torch.float32 tensor, got {getattr(points, "dtype", type(points))}')
+    if points.dim() != 3 or points.shape[0] != n or points.shape[2] != 2 or not 1 <= points.shape[1] <= MAX_POINTS or not points.is_contiguous():
+        raise ValueError(f'points must be contiguous [{n}, P, 2] with 1 <= P <= {MAX_POINTS}, got {tuple(points.shape)}')
+    if points.device != device:
+        raise ValueError(f'points live on {points.device}, the env on {device}')
+    return points
+
+
+def check_out(out, n, spec, device):
+    """`out=` of BatchedEnv.probe(): a Probe whose fields are None (skipped) or contiguous [N, n_points] tensors of the field's dtype on the
+    env's device; at least one must be given."""
+    if not isinstance(out, Probe):
+        raise TypeError('out must be a probe_device.Probe (None fields are skipped)')
+    shape = (n, spec.n_points)
+    for (name, dtype), t in zip(FIELDS, out):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError(f'out.{name} must be a {dtype} tensor, got {getattr(t, "dtype", type(t))}')
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f'out.{name} must be contiguous {shape}, got {tuple(t.shape)}')
+        if t.device != device:
+            raise ValueError(f'out.{name} lives on {t.device}, the env on {device}')
+    if all(t is None for t in out):
+        raise ValueError('out holds no tensor: at least one output must be given')
+    return out

@@ -189,6 +189,35 @@ class BatchedEnv:
         self._last_scan_mask = m  # keep alive until the stream has consumed it
         return rng, hit
 
+    def probe(self, points, spec=None, mask=None, out=None):
+        """Point probes: for P query points per env (`points` float32 [N, P, 2] on this device, 1 <= P <= 512) a namedtuple
+        Probe(clearance, nearest, sight, blocker, path, via), each [N, P] on this device, from ONE launch on the current stream
+        (probe_device.py, include/hrl_probe.h).  clearance / nearest: the signed distance to the nearest shape and its code (class |
+        index << 8, probe_device.decode); sight / blocker: how far the segment from the robot to the point runs free and what stops it (0 =
+        the point is visible); path / via: the length of the shortest way round the maze box for a disc of radius spec.margin and the
+        corner it first turns at (probe_device.corner_table).  `spec`: an hrl_probe_spec (probe_device.default_spec(cfg, frame, n_points));
+        None = world-frame points, all classes, margin = the torso's radius.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh
+        tensors).  `out`: a Probe of tensors to reuse; a None field is not computed.  The probes are of the state / items / aux tensors as
+        they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import probe_device as P
+        points = P.check_points(points, self.num_envs, self.device)
+        if spec is None:
+            spec = getattr(self, '_default_probe', None)
+            if spec is None or spec.n_points != points.shape[1]:
+                spec = self._default_probe = P.default_spec(self.cfg, 'world', points.shape[1])
+        elif spec.n_points != points.shape[1]:
+            raise ValueError(f'spec.n_points is {spec.n_points}, points hold {points.shape[1]} per env')
+        if out is None:
+            make = torch.empty if mask is None else torch.zeros
+            out = P.Probe(*(make(self.num_envs, spec.n_points, dtype=dtype, device=self.device) for _, dtype in P.FIELDS))
+        else:
+            P.check_out(out, self.num_envs, spec, self.device)
+        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            P.probe(self.cfg, self._bufs_ref, spec, points, None if m is None else m.data_ptr(), out, self._stream())
+        self._last_probe_mask = m  # keep alive until the stream has consumed it
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
