@@ -1,7 +1,7 @@
 """Build the gfx950 HIP libraries in-tree: hrl_pybullet_envs_amd/libhrl_envs_hip.so (the step, include/hrl_envs.h),
 hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h), hrl_pybullet_envs_amd/libhrl_scan_hip.so
-(the batched range scanner, include/hrl_scan.h) and hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
-include/hrl_probe.h).
+(the batched range scanner, include/hrl_scan.h), hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
+include/hrl_probe.h) and hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -19,6 +19,8 @@ SCAN_LIB = os.path.join(PKG, 'libhrl_scan_hip.so')
 SCAN_SOURCES = ['scan_hip.hip', 'scan_core.h', 'render_core.h', 'step_core.h', 'host_cfg.h']   # likewise: it reads the renderer's table, not its library
 PROBE_LIB = os.path.join(PKG, 'libhrl_probe_hip.so')
 PROBE_SOURCES = ['probe_hip.hip', 'probe_core.h', 'scan_core.h', 'render_core.h', 'step_core.h', 'host_cfg.h']   # likewise: the scanner's intersections through an include
+FIELD_LIB = os.path.join(PKG, 'libhrl_field_hip.so')
+FIELD_SOURCES = ['field_hip.hip', 'field_core.h'] + PROBE_SOURCES[1:]   # likewise: the probe's table and clearances through an include
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -70,13 +72,20 @@ def build_probe(force=False, verbose=False):
     return _compile(PROBE_LIB, 'probe_hip.hip', verbose)
 
 
+def build_field(force=False, verbose=False):
+    if not force and not _stale(FIELD_LIB, FIELD_SOURCES, ('hrl_envs.h', 'hrl_render.h', 'hrl_scan.h', 'hrl_probe.h', 'hrl_field.h')):
+        return FIELD_LIB
+    return _compile(FIELD_LIB, 'field_hip.hip', verbose)
+
+
 def build(force=False, verbose=False):
-    """The four libraries; returns the step library's path."""
+    """The five libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     build_render(force, verbose)
     build_scan(force, verbose)
     build_probe(force, verbose)
+    build_field(force, verbose)
     return LIB
 
 
@@ -85,3 +94,4 @@ if __name__ == '__main__':
     print(RENDER_LIB)
     print(SCAN_LIB)
     print(PROBE_LIB)
+    print(FIELD_LIB)

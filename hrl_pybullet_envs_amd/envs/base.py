@@ -212,6 +212,11 @@ class BatchedGymEnv:
         device, for `points` float32 [N, P, 2] (BatchedEnv.probe; probe_device.default_spec for other frames and margins)."""
         return self._backend().probe(points, spec, mask, out)
 
+    def field_batch(self, spec=None, mask=None, out=None):
+        """The navigation field of EVERY env in one launch: Field(dist float32, parent uint8), each [N, H, W] on the env's device and on
+        the grid of render_batch() (BatchedEnv.field; field_device.default_spec for other grids, obstacles and sources)."""
+        return self._backend().field(spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

@@ -218,6 +218,34 @@ class BatchedEnv:
         self._last_probe_mask = m  # keep alive until the stream has consumed it
         return out
 
+    def field(self, spec=None, mask=None, out=None):
+        """The navigation field of every env: a namedtuple Field(dist float32 [N, H, W], parent uint8 [N, H, W]) on this device, from ONE
+        launch on the current stream (field_device.py, include/hrl_field.h).  On the renderer's pixel grid, for a disc of radius
+        spec.margin among the shapes of spec.blocking: dist = the length of the shortest 8-connected way from the cell to the nearest
+        source cell (spec.sources: the robot, the target, food, poison), 0 on a source, +inf where there is no way; parent = the direction
+        code 0..7 of that way's first step (field_device.DIRECTIONS, direction_vectors), or SOURCE / UNREACHED / BLOCKED.  `spec`: an
+        hrl_field_spec (field_device.default_spec(cfg, mode, width, height)); None = the 64 x 64 world grid of the whole arena towards the
+        kind's goal.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh tensors).  `out`: a Field of tensors to reuse; a None
+        member is not computed.  The field is of the state / items / aux tensors as they are; nothing else is read or written.
+        Capturable: call it once before the capture."""
+        from . import field_device as F
+        if spec is None:
+            spec = getattr(self, '_default_field', None)
+            if spec is None:
+                spec = self._default_field = F.default_spec(self.cfg)
+        if out is None:
+            if not (F.MIN_SIZE <= spec.width <= F.MAX_SIZE and F.MIN_SIZE <= spec.height <= F.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
+                raise ValueError(f'spec.width and spec.height must be within {F.MIN_SIZE}..{F.MAX_SIZE}, got {spec.width} x {spec.height}')
+            make = torch.empty if mask is None else torch.zeros
+            out = F.Field(*(make(self.num_envs, spec.height, spec.width, dtype=dtype, device=self.device) for _, dtype in F.FIELDS))
+        else:
+            F.check_out(out, self.num_envs, spec, self.device)
+        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            F.field(self.cfg, self._bufs_ref, spec, None if m is None else m.data_ptr(), out, self._stream())
+        self._last_field_mask = m  # keep alive until the stream has consumed it
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)

@@ -1,0 +1,255 @@
+"""Shared by tests/test_field_host.py and tests/test_gpu_field.py: the ctypes binding of tests/field_host/libfield_host.so (the host build
+of csrc/field_core.h), an independent fp64 numpy reference written from include/hrl_field.h alone (world coordinates, textbook signed
+distances, Dijkstra with heapq), and the states and specs the tests compute fields of.  Test infrastructure only."""
+import collections
+import ctypes as C
+import heapq
+import os
+import subprocess
+
+import numpy as np
+
+import probe_cases as pc
+import render_cases as rc
+from hrl_pybullet_envs_amd import _capi as K
+from hrl_pybullet_envs_amd import field_device as F
+
+ROOT = rc.ROOT
+DIR = os.path.join(ROOT, 'tests', 'field_host')
+KINDS = rc.KINDS
+MODES = rc.MODES
+SIZES = ((8, 8), (24, 40), (64, 8), (64, 64))   # width, height: 64 cells | 960, no multiple of 256 | an edge shape | the maximum
+GPU_SIZES = SIZES[:3] + ((8, 64), (64, 64))
+MARGINS = (0.0, 0.25, 0.4)
+SOURCE_BITS = (F.ROBOT, F.FOOD, F.POISON, F.TARGET)
+SOURCE_SETS = tuple(sum(b for i, b in enumerate(SOURCE_BITS) if m >> i & 1) for m in range(1, 16))   # every admissible source set
+DEFAULT_BLOCKING = F.WALL | F.BOX | F.POISON
+# world grids on which no wall, box side or arena edge grown by 0, 0.25 or 0.4 m runs along a row or column of cell centres at 8, 24 or 64
+# columns (checked by the reference itself before anything is compared: test_field_host.py)
+WORLD_HALF = {K.HRL_ANT_FLAT: 6.1, K.HRL_ANT_GATHER: 7.7, K.HRL_ANT_MAZE: 9.3, K.HRL_POINT_GATHER: 7.7, K.HRL_ANT_MAZE_MJ: 9.3, K.HRL_ANT_FLAGRUN: 6.1}
+WORLD_CENTRE = (0.13, -0.21)   # ... and no default target, start or spread robot on the edge between two cells
+EGO_HALF = 3.1
+JACOBI, FORWARD, REVERSE = 0, 1, 2
+NAMES = ('dist', 'parent')
+DTYPES = (np.float32, np.uint8)
+Field = collections.namedtuple('Field', NAMES)   # of numpy arrays
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        subprocess.check_call(['make', '-s', '-C', DIR, 'libfield_host.so'])
+        L = C.CDLL(os.path.join(DIR, 'libfield_host.so'))
+        L.field_host.argtypes = [C.POINTER(K.hrl_config), C.POINTER(K.hrl_buffers), C.POINTER(F.hrl_field_spec), C.c_void_p, C.POINTER(F.hrl_field_out), C.c_int, C.c_void_p]
+        L.field_host_last_error.restype = C.c_char_p
+        L.field_host_default_spec.argtypes = [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(F.hrl_field_spec)]
+        L.field_sizeof_spec.restype = C.c_ulonglong
+        L.field_sizeof_out.restype = C.c_ulonglong
+        L.field_validate_spec.argtypes, L.field_validate_spec.restype = [C.POINTER(F.hrl_field_spec)], C.c_char_p
+        L.field_check_case.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_ulonglong)]
+        _lib = L
+    return _lib
+
+
+def check_program():
+    subprocess.check_call(['make', '-s', '-C', DIR, 'field_check_main'])
+    return os.path.join(DIR, 'field_check_main')
+
+
+ptr = rc.ptr
+
+
+def spec_of(size, mode, margin, sources, blocking=DEFAULT_BLOCKING, half=None, centre=(0.0, 0.0), kind=None):
+    w, h = size
+    he = half if half is not None else (WORLD_HALF[kind] if mode == F.HRL_VIEW_WORLD else EGO_HALF)
+    return F.hrl_field_spec(width=w, height=h, mode=mode, centre=(C.c_float * 2)(*centre), half_extent=he, blocking=blocking, sources=sources, margin=margin)
+
+
+def field_host(cfg, state, items, aux, spec, mask=None, out=None, want=NAMES, schedule=JACOBI, rounds=None, expect_ok=True):
+    """The host build's field of (state [N, 32] f32, items [N, stride] f32 or None, aux [N, 4] i32): a Field of arrays [N, H, W]; the
+    members not in `want` are None.  `out`: a Field of arrays (None members are passed as NULL) to write into; `rounds`: an int32 [N]
+    array that receives the rounds each env ran."""
+    state, aux = np.ascontiguousarray(state, np.float32), np.ascontiguousarray(aux, np.int32)
+    items = None if items is None else np.ascontiguousarray(items, np.float32)
+    n = cfg.num_envs
+    assert state.shape == (n, K.HRL_STATE_STRIDE) and aux.shape == (n, K.HRL_AUX_STRIDE)
+    if out is None:
+        shape = (n, min(max(spec.height, 1), 64), min(max(spec.width, 1), 64))
+        out = Field(*(np.zeros(shape, dt) if name in want else None for name, dt in zip(NAMES, DTYPES)))
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    b = K.make_buffers(ptr(state), ptr(items), ptr(aux), None, None, None, None, None)
+    o = F.hrl_field_out(**{name: ptr(a) for name, a in zip(NAMES, out)})
+    code = lib().field_host(C.byref(cfg), C.byref(b), C.byref(spec), ptr(m), C.byref(o), schedule, ptr(rounds))
+    if expect_ok:
+        assert code == K.HRL_OK, lib().field_host_last_error()
+        return out
+    return code, lib().field_host_last_error().decode()
+
+
+def bits(field):
+    return [None if x is None else (x.view(np.uint32) if x.dtype == np.float32 else x) for x in field]
+
+
+def same(a, b):
+    return all((x is None and y is None) or np.array_equal(x, y) for x, y in zip(bits(a), bits(b)))
+
+
+# ------------------------------------------------------------------------------------------------ the fp64 reference
+W2 = float(np.float32(1.41421354))
+BAND = 1e-4   # metres: a cell whose clearance is this close to the margin (or whose centre is this close to a source's half-cell bound) is exempt
+
+
+def cell_size(spec):
+    return 2.0 / spec.width * float(spec.half_extent)
+
+
+def centres(st, spec):
+    """World positions [H, W, 2] of the cell centres and their grid coordinates u [W], v [H], fp64."""
+    w, h, he = spec.width, spec.height, float(spec.half_extent)
+    c, right, up = rc.frame(st, spec)
+    u = ((np.arange(w) + 0.5) * 2 / w - 1) * he
+    v = (h / w - (np.arange(h) + 0.5) * 2 / w) * he
+    uu, vv = np.meshgrid(u, v)
+    return c + uu[..., None] * right + vv[..., None] * up, u, v, (c, right, up)
+
+
+def clearance(typ, p, x, y):
+    if typ == 'half':
+        (nx, ny), off = p
+        return nx * x + ny * y + off
+    if typ == 'rect':
+        (cx, cy), (hx, hy) = p
+        return rc._sd_rect(x, y, (cx, cy), hx, hy)
+    (cx, cy), r = p
+    return np.hypot(x - cx, y - cy) - r
+
+
+def geometry(cfg, st, items, aux, spec):
+    """(blocked, source, near) [H, W] bool of one env in fp64: blocked = some kept shape leaves less than margin; source = a source cell
+    (free whatever `blocked` says); near = the cell is within BAND of changing either verdict.  (The robot of an ego grid is no near
+    case: it stands on the common corner of the four central cells by construction, and `<=` makes all four sources.)"""
+    pos, u, v, (c, right, up) = centres(st, spec)
+    x, y = pos[..., 0], pos[..., 1]
+    h, w = spec.height, spec.width
+    margin, half = float(spec.margin), cell_size(spec) / 2
+    robot = np.array([st[0], st[1]], float)
+    robot_ok = bool(np.isfinite(robot).all())
+    blocked, near, source = np.zeros((h, w), bool), np.zeros((h, w), bool), np.zeros((h, w), bool)
+    if spec.mode != F.HRL_VIEW_WORLD and not robot_ok:
+        return np.ones((h, w), bool), source, near
+    points = []
+    if spec.sources & F.ROBOT and robot_ok:
+        if spec.mode == F.HRL_VIEW_WORLD:
+            points.append(robot)
+        else:   # an ego grid is centred on the robot and W, H are even: the robot stands on the corner of the four central cells, an exact tie
+            source[h // 2 - 1:h // 2 + 1, w // 2 - 1:w // 2 + 1] = True
+    for cls, _, typ, p in pc.shapes(cfg, items, aux):
+        if not np.isfinite([q for part in p for q in np.ravel(part)]).all():
+            continue
+        if spec.blocking & cls:
+            d = clearance(typ, p, x, y)
+            blocked |= d < margin
+            near |= np.abs(d - margin) < BAND
+        if spec.sources & cls and typ != 'half':
+            points.append(np.array(p[0], float))
+    for s in points:
+        su, sv = (s - c) @ right, (s - c) @ up
+        du, dv = np.abs(u - su)[None, :], np.abs(v - sv)[:, None]
+        source |= (du <= half) & (dv <= half)
+        near |= ((np.abs(du - half) < BAND) & (dv <= half + BAND)) | ((np.abs(dv - half) < BAND) & (du <= half + BAND))
+    return blocked & ~source, source, near
+
+
+STEPS = F.DIRECTIONS   # (dcol, drow) of code 0..7
+
+
+def admissible(free):
+    """[8, H, W] bool: step k from the cell is admissible on the free mask `free` [H, W]."""
+    h, w = free.shape
+    pad = np.zeros((h + 2, w + 2), bool)
+    pad[1:-1, 1:-1] = free
+    nb = [pad[1 + dr:1 + dr + h, 1 + dc:1 + dc + w] for dc, dr in STEPS]
+    return np.stack([free & nb[k] & (True if k % 2 == 0 else nb[k - 1] & nb[(k + 1) % 8]) for k in range(8)])
+
+
+def dijkstra(free, source, cell):
+    """fp64 shortest 8-connected ways on the mask: (dist [H, W], cand [8, H, W]) with cand[k] = dist(neighbour k) + w_k, inf where the
+    step is not admissible."""
+    h, w = free.shape
+    adm = admissible(free)
+    wk = [cell if k % 2 == 0 else cell * W2 for k in range(8)]
+    dist = np.full((h, w), np.inf)
+    heap = []
+    for i, j in np.argwhere(source):
+        dist[i, j] = 0.0
+        heap.append((0.0, int(i), int(j)))
+    heapq.heapify(heap)
+    adml, distl = adm.tolist(), dist.tolist()
+    while heap:
+        d, i, j = heapq.heappop(heap)
+        if d > distl[i][j]:
+            continue
+        for k, (dc, dr) in enumerate(STEPS):
+            if adml[k][i][j]:   # (admissibility is symmetric: the way back needs the same four cells)
+                nd, ni, nj = d + wk[k], i + dr, j + dc
+                if nd < distl[ni][nj]:
+                    distl[ni][nj] = nd
+                    heapq.heappush(heap, (nd, ni, nj))
+    dist = np.array(distl)
+    pad = np.full((h + 2, w + 2), np.inf)
+    pad[1:-1, 1:-1] = dist
+    cand = np.stack([np.where(adm[k], pad[1 + dr:1 + dr + h, 1 + dc:1 + dc + w] + wk[k], np.inf) for k, (dc, dr) in enumerate(STEPS)])
+    return dist, cand
+
+
+def reference(cfg, st, items, aux, spec):
+    """(dist, blocked, source, near) of one env entirely in fp64."""
+    blocked, source, near = geometry(cfg, st, items, aux, spec)
+    dist, _ = dijkstra(~blocked, source, cell_size(spec))
+    return np.where(blocked, np.inf, dist), blocked, source, near
+
+
+def check_propagation(got, spec, tol):
+    """One env's host field against fp64 Dijkstra ON THE HOST BUILD'S OWN mask and source set.  Returns the worst |dist - reference| over
+    the reached cells after asserting: +inf / UNREACHED agree exactly, dist within tol, and the step `parent` names is, in the
+    reference, within tol of the best one (so it IS the best one wherever the best and the second best differ by more than tol)."""
+    dist, parent = got
+    blocked, source = parent == F.BLOCKED, parent == F.SOURCE
+    ref, cand = dijkstra(~blocked, source, cell_size(spec))
+    ref = np.where(blocked, np.inf, ref)
+    assert np.array_equal(np.isinf(dist), np.isinf(ref))
+    assert np.array_equal(parent == F.UNREACHED, np.isinf(ref) & ~blocked)
+    assert (dist[source] == 0).all() and (dist[~np.isinf(dist) & ~source] > 0).all()
+    reached = np.isfinite(ref) & ~source
+    err = np.abs(dist[reached].astype(float) - ref[reached])
+    assert (parent[reached] < 8).all()
+    ii, jj = np.nonzero(reached)
+    chosen = cand[parent[reached], ii, jj]
+    assert (chosen - ref[reached] <= tol).all(), float((chosen - ref[reached]).max())
+    worst = float(err.max()) if err.size else 0.0
+    assert worst <= tol, worst
+    return worst
+
+
+# ------------------------------------------------------------------------------------------------ states
+hand_made = rc.hand_made
+spread = pc.spread
+far_targets = rc.far_targets
+hostile = pc.hostile
+
+
+def follow(parent, row, col, limit):
+    """Walks `parent` [H, W] from (row, col): the number of steps until a SOURCE cell, or -1 when the walk leaves the grid, meets a cell
+    without a direction or takes more than `limit` steps."""
+    h, w = parent.shape
+    for n in range(limit + 1):
+        if not (0 <= row < h and 0 <= col < w):
+            return -1
+        k = int(parent[row, col])
+        if k == F.SOURCE:
+            return n
+        if k > 7:
+            return -1
+        row, col = row + STEPS[k][1], col + STEPS[k][0]
+    return -1
