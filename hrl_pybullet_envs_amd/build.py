@@ -13,14 +13,13 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libhrl_envs_hip.so')
 SOURCES = ['hrl_hip.hip', 'step_core.h', 'host_cfg.h']
-RENDER_LIB = os.path.join(PKG, 'libhrl_render_hip.so')
-RENDER_SOURCES = ['render_hip.hip', 'render_core.h', 'step_core.h', 'host_cfg.h']   # a library of its own: the step library's code object stays what it was
-SCAN_LIB = os.path.join(PKG, 'libhrl_scan_hip.so')
-SCAN_SOURCES = ['scan_hip.hip', 'scan_core.h', 'render_core.h', 'step_core.h', 'host_cfg.h']   # likewise: it reads the renderer's table, not its library
-PROBE_LIB = os.path.join(PKG, 'libhrl_probe_hip.so')
-PROBE_SOURCES = ['probe_hip.hip', 'probe_core.h', 'scan_core.h', 'render_core.h', 'step_core.h', 'host_cfg.h']   # likewise: the scanner's intersections through an include
-FIELD_LIB = os.path.join(PKG, 'libhrl_field_hip.so')
-FIELD_SOURCES = ['field_hip.hip', 'field_core.h'] + PROBE_SOURCES[1:]   # likewise: the probe's table and clearances through an include
+# The sensor libraries in build order: (name, library, source, specification, public header).  Each is a library of its own -- the step
+# library's code object stays what it was -- and reads its predecessor's table through an include, not its library: what a sensor depends
+# on is its own three files plus everything its predecessor depends on.  csrc/sensor_launch.h is the host side of all four.
+SENSORS = [('render', 'libhrl_render_hip.so', 'render_hip.hip', 'render_core.h', 'hrl_render.h'),
+           ('scan', 'libhrl_scan_hip.so', 'scan_hip.hip', 'scan_core.h', 'hrl_scan.h'),
+           ('probe', 'libhrl_probe_hip.so', 'probe_hip.hip', 'probe_core.h', 'hrl_probe.h'),
+           ('field', 'libhrl_field_hip.so', 'field_hip.hip', 'field_core.h', 'hrl_field.h')]
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -54,44 +53,42 @@ def _compile(lib, source, verbose):
     return lib
 
 
+def build_sensor(name, force=False, verbose=False):
+    """Sensor library `name` of SENSORS; returns its path."""
+    upto = [n for n, *_ in SENSORS].index(name) + 1
+    lib, source = os.path.join(PKG, SENSORS[upto - 1][1]), SENSORS[upto - 1][2]
+    sources = [source, 'sensor_launch.h'] + [core for *_, core, _ in SENSORS[:upto]] + SOURCES[1:]
+    if force or _stale(lib, sources, ['hrl_envs.h'] + [header for *_, header in SENSORS[:upto]]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build_render(force=False, verbose=False):
-    if not force and not _stale(RENDER_LIB, RENDER_SOURCES, ('hrl_envs.h', 'hrl_render.h')):
-        return RENDER_LIB
-    return _compile(RENDER_LIB, 'render_hip.hip', verbose)
+    return build_sensor('render', force, verbose)
 
 
 def build_scan(force=False, verbose=False):
-    if not force and not _stale(SCAN_LIB, SCAN_SOURCES, ('hrl_envs.h', 'hrl_render.h', 'hrl_scan.h')):
-        return SCAN_LIB
-    return _compile(SCAN_LIB, 'scan_hip.hip', verbose)
+    return build_sensor('scan', force, verbose)
 
 
 def build_probe(force=False, verbose=False):
-    if not force and not _stale(PROBE_LIB, PROBE_SOURCES, ('hrl_envs.h', 'hrl_render.h', 'hrl_scan.h', 'hrl_probe.h')):
-        return PROBE_LIB
-    return _compile(PROBE_LIB, 'probe_hip.hip', verbose)
+    return build_sensor('probe', force, verbose)
 
 
 def build_field(force=False, verbose=False):
-    if not force and not _stale(FIELD_LIB, FIELD_SOURCES, ('hrl_envs.h', 'hrl_render.h', 'hrl_scan.h', 'hrl_probe.h', 'hrl_field.h')):
-        return FIELD_LIB
-    return _compile(FIELD_LIB, 'field_hip.hip', verbose)
+    return build_sensor('field', force, verbose)
 
 
 def build(force=False, verbose=False):
     """The five libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
-    build_render(force, verbose)
-    build_scan(force, verbose)
-    build_probe(force, verbose)
-    build_field(force, verbose)
+    for name, *_ in SENSORS:
+        build_sensor(name, force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    print(RENDER_LIB)
-    print(SCAN_LIB)
-    print(PROBE_LIB)
-    print(FIELD_LIB)
+    for _, lib, *_ in SENSORS:
+        print(os.path.join(PKG, lib))

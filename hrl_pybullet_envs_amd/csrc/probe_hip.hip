@@ -8,29 +8,21 @@
  * wave 0 then hold corner node lane & 3 each and run the three Jacobi rounds through lane shuffles, and lanes 0..3 leave the nodes and
  * g[] in LDS.  Each wave then takes runs of 64 points, lane = point: a lane reads one float2 and stores one 4-byte value per requested
  * output, so the lanes of a wave write 256 consecutive bytes of each tensor.
+ *
+ * The host side of the entry point -- the guards, the cache of kernel constants, the launch epilogue -- is sensor_launch.h, shared with
+ * the other sensor libraries.
  */
 #include <hip/hip_runtime.h>
 
-#include <string.h>
-
-#include <mutex>
-#include <string>
-#include <vector>
-
 #include "probe_core.h"
+#include "sensor_launch.h"
 
 using namespace hrl;
 using namespace hrl::probe;
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char *what) { return fail(HRL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
+constexpr char LIB[] = "hrl_probe";
 constexpr int MAX_BLOCK = 256;
 
 __global__ __launch_bounds__(MAX_BLOCK) void probe_kernel(const DevCfg *cfg, const float *state, const float *items, const int32_t *aux, const uint8_t *mask,
@@ -89,46 +81,6 @@ __global__ __launch_bounds__(MAX_BLOCK) void probe_kernel(const DevCfg *cfg, con
     }
 }
 
-/* The kernel constants of every (device, config) this process has probed, uploaded once and kept: a launch with a known config
- * allocates and copies nothing (graph capture).  Entries are never freed -- a captured graph may hold their address. */
-struct CacheEntry { int device; hrl_config cfg; DevCfg *d_dc; };
-std::mutex g_mutex;
-std::vector<CacheEntry> g_cache;
-constexpr size_t CACHE_MAX = 1024;
-
-int devcfg_for(const hrl_config *cfg, int device, DevCfg **out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    for (const CacheEntry &e : g_cache)
-        if (e.device == device && memcmp(&e.cfg, cfg, sizeof(hrl_config)) == 0) { *out = e.d_dc; return HRL_OK; }
-    if (g_cache.size() >= CACHE_MAX) return fail(HRL_ERR_BAD_ARG, "hrl_probe: more than 1024 distinct configs probed by this process (their constants are kept for captured graphs)");
-    DevCfg dc, *d = nullptr;
-    build_devcfg(*cfg, dc);
-    hipError_t e = hipMalloc((void **)&d, sizeof(DevCfg));
-    if (e == hipSuccess) e = hipMemcpy(d, &dc, sizeof(DevCfg), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        return hip_fail(e, "hrl_probe: device constants (the first call with a config must happen outside stream capture)");
-    }
-    g_cache.push_back(CacheEntry{device, *cfg, d});
-    *out = d;
-    return HRL_OK;
-}
-
-/* the device guard of the step library (hrl_hip.hip: check_call): a launch goes to the CURRENT device, so the buffers must live there */
-int check_device(const void *p, const char *name, int cur) {
-    if (!p) return HRL_OK; /* (an output that is not asked for) */
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(HRL_ERR_BAD_ARG, std::string("hrl_probe: ") + name + " is not memory the HIP runtime knows (device pointers are required)");
-    }
-    if (a.type == hipMemoryTypeDevice && a.device != cur)
-        return fail(HRL_ERR_BAD_ARG, std::string("hrl_probe: ") + name + " lives on HIP device " + std::to_string(a.device) + ", the current device is " + std::to_string(cur) +
-                                         ": hipSetDevice(" + std::to_string(a.device) + ") before calling");
-    return HRL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -143,39 +95,26 @@ int hrl_probe(const hrl_config *cfg, const hrl_buffers *b, const hrl_probe_spec 
     if (why.empty()) why = validate_spec(spec);
     if (why.empty()) why = validate_out(out);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_probe: " + why);
-    if (!b) return fail(HRL_ERR_BAD_ARG, "hrl_probe: null buffer record");
-    if (b->struct_size < HRL_BUFFERS_SIZE_V7_BASE || b->struct_size > 4096 || b->struct_size % sizeof(void *) != 0)
-        return fail(HRL_ERR_BAD_ARG, "hrl_probe: hrl_buffers.struct_size is not the size of a known layout: initialise the record with hrl_buffers_init() (include/hrl_envs.h)");
-    if (!b->state || !b->aux) return fail(HRL_ERR_BAD_ARG, "hrl_probe: null state or aux");
+    if (const int rc = check_record(LIB, b, "hrl_probe: null state or aux")) return rc;
     if (!points) return fail(HRL_ERR_BAD_ARG, "hrl_probe: null points");
     if (reinterpret_cast<uintptr_t>(points) % 8 != 0) return fail(HRL_ERR_BAD_ARG, "hrl_probe: points must be 8-byte aligned");
     const void *outs[6] = {out->clearance, out->nearest, out->sight, out->blocker, out->path, out->via};
     const char *names[6] = {"clearance", "nearest", "sight", "blocker", "path", "via"};
     for (int i = 0; i < 6; ++i)
         if (reinterpret_cast<uintptr_t>(outs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_probe: ") + names[i] + " must be 4-byte aligned");
-    int ndev = 0, cur = -1;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HRL_ERR_NO_DEVICE, "hrl_probe: no HIP device (this library has no CPU path)");
-    }
-    if (hipGetDevice(&cur) != hipSuccess) return fail(HRL_ERR_HIP, "hrl_probe: hipGetDevice");
-    /* (a stream that is being captured: the pointers were looked at by the call that came before the capture) */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    if (cap == hipStreamCaptureStatusNone) {
-        if (const int rc = check_device(b->state, "state", cur)) return rc;
-        if (const int rc = check_device(points, "points", cur)) return rc;
-        for (int i = 0; i < 6; ++i)
-            if (const int rc = check_device(outs[i], names[i], cur)) return rc;
-    }
+    Context ctx;
+    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
+    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
+    if (const int rc = check_device(LIB, ctx, points, "points")) return rc;
+    for (int i = 0; i < 6; ++i)
+        if (const int rc = check_device(LIB, ctx, outs[i], names[i])) return rc;
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(cfg, cur, &d_dc)) return rc;
+    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
     const int waves = (spec->n_points + 63) / 64; /* 64 points do not carry three idle waves */
     const int block = 64 * (waves < 4 ? waves : 4);
     hipLaunchKernelGGL(probe_kernel, dim3(cfg->num_envs), dim3(block), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, mask, (const float2 *)points, *out, *spec);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HRL_OK : hip_fail(e, "hrl_probe launch");
+    return launched(LIB);
 }
 
 const char *hrl_probe_last_error(void) { return g_err.c_str(); }

@@ -9,29 +9,21 @@
  * 4096 x 64 x 64 frame.  The list is wave-uniform (it lives in scalar registers, the table reads are LDS broadcasts), the 16 colours of
  * a strip live in registers under fully unrolled loops (no scratch), and a lane stores its 48 bytes as three 16-byte vectors; the
  * lanes of a wave write 3 KB of consecutive addresses.
+ *
+ * The host side of the entry point -- the guards, the cache of kernel constants, the launch epilogue -- is sensor_launch.h, shared with
+ * the other sensor libraries.
  */
 #include <hip/hip_runtime.h>
 
-#include <string.h>
-
-#include <mutex>
-#include <string>
-#include <vector>
-
 #include "render_core.h"
+#include "sensor_launch.h"
 
 using namespace hrl;
 using namespace hrl::render;
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char *what) { return fail(HRL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
+constexpr char LIB[] = "hrl_render";
 constexpr int BLOCK = 256;
 
 __global__ __launch_bounds__(BLOCK) void render_kernel(const DevCfg *cfg, const float *state, const float *items, const int32_t *aux, const uint8_t *mask,
@@ -77,45 +69,6 @@ __global__ __launch_bounds__(BLOCK) void render_kernel(const DevCfg *cfg, const 
     }
 }
 
-/* The kernel constants of every (device, config) this process has rendered, uploaded once and kept: a launch with a known config
- * allocates and copies nothing (graph capture).  Entries are never freed -- a captured graph may hold their address. */
-struct CacheEntry { int device; hrl_config cfg; DevCfg *d_dc; };
-std::mutex g_mutex;
-std::vector<CacheEntry> g_cache;
-constexpr size_t CACHE_MAX = 1024; /* 0.7 MB of constants */
-
-int devcfg_for(const hrl_config *cfg, int device, DevCfg **out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    for (const CacheEntry &e : g_cache)
-        if (e.device == device && memcmp(&e.cfg, cfg, sizeof(hrl_config)) == 0) { *out = e.d_dc; return HRL_OK; }
-    if (g_cache.size() >= CACHE_MAX) return fail(HRL_ERR_BAD_ARG, "hrl_render: more than 1024 distinct configs rendered by this process (their constants are kept for captured graphs)");
-    DevCfg dc, *d = nullptr;
-    build_devcfg(*cfg, dc);
-    hipError_t e = hipMalloc((void **)&d, sizeof(DevCfg));
-    if (e == hipSuccess) e = hipMemcpy(d, &dc, sizeof(DevCfg), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        return hip_fail(e, "hrl_render: device constants (the first call with a config must happen outside stream capture)");
-    }
-    g_cache.push_back(CacheEntry{device, *cfg, d});
-    *out = d;
-    return HRL_OK;
-}
-
-/* the device guard of the step library (hrl_hip.hip: check_call): a launch goes to the CURRENT device, so the buffers must live there */
-int check_device(const void *p, const char *name, int cur) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(HRL_ERR_BAD_ARG, std::string("hrl_render: ") + name + " is not memory the HIP runtime knows (device pointers are required)");
-    }
-    if (a.type == hipMemoryTypeDevice && a.device != cur)
-        return fail(HRL_ERR_BAD_ARG, std::string("hrl_render: ") + name + " lives on HIP device " + std::to_string(a.device) + ", the current device is " + std::to_string(cur) +
-                                         ": hipSetDevice(" + std::to_string(a.device) + ") before calling");
-    return HRL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -129,30 +82,19 @@ int hrl_render(const hrl_config *cfg, const hrl_buffers *b, const hrl_view *view
     std::string why = validate(cfg);
     if (why.empty()) why = validate_view(view);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_render: " + why);
-    if (!b) return fail(HRL_ERR_BAD_ARG, "hrl_render: null buffer record");
-    if (b->struct_size < HRL_BUFFERS_SIZE_V7_BASE || b->struct_size > 4096 || b->struct_size % sizeof(void *) != 0)
-        return fail(HRL_ERR_BAD_ARG, "hrl_render: hrl_buffers.struct_size is not the size of a known layout: initialise the record with hrl_buffers_init() (include/hrl_envs.h)");
-    if (!b->state || !b->aux || !rgb) return fail(HRL_ERR_BAD_ARG, "hrl_render: null state, aux or rgb");
+    constexpr char NULLS[] = "hrl_render: null state, aux or rgb";
+    if (const int rc = check_record(LIB, b, NULLS)) return rc;
+    if (!rgb) return fail(HRL_ERR_BAD_ARG, NULLS);
     if (reinterpret_cast<uintptr_t>(rgb) % 16 != 0) return fail(HRL_ERR_BAD_ARG, "hrl_render: rgb must be 16-byte aligned (a strip of 16 pixels is stored as three 16-byte vectors)");
-    int ndev = 0, cur = -1;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HRL_ERR_NO_DEVICE, "hrl_render: no HIP device (this library has no CPU path)");
-    }
-    if (hipGetDevice(&cur) != hipSuccess) return fail(HRL_ERR_HIP, "hrl_render: hipGetDevice");
-    /* (a stream that is being captured: the pointers were looked at by the call that came before the capture) */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    if (cap == hipStreamCaptureStatusNone) {
-        if (const int rc = check_device(b->state, "state", cur)) return rc;
-        if (const int rc = check_device(rgb, "rgb", cur)) return rc;
-    }
+    Context ctx;
+    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
+    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
+    if (const int rc = check_device(LIB, ctx, rgb, "rgb")) return rc;
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(cfg, cur, &d_dc)) return rc;
+    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
     hipLaunchKernelGGL(render_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, mask, rgb, *view);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HRL_OK : hip_fail(e, "hrl_render launch");
+    return launched(LIB);
 }
 
 const char *hrl_render_last_error(void) { return g_err.c_str(); }

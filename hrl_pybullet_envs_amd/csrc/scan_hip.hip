@@ -7,29 +7,21 @@
  * verdicts, two ballots give the list of surviving slots -- wave-uniform, so it lives in scalar registers and the walk's table reads are
  * LDS broadcasts -- and lane = ray walks only the set bits in slot order.  A lane stores one float and one int32; the lanes of a wave
  * write 256 consecutive bytes of each output.
+ *
+ * The host side of the entry point -- the guards, the cache of kernel constants, the launch epilogue -- is sensor_launch.h, shared with
+ * the other sensor libraries.
  */
 #include <hip/hip_runtime.h>
 
-#include <string.h>
-
-#include <mutex>
-#include <string>
-#include <vector>
-
 #include "scan_core.h"
+#include "sensor_launch.h"
 
 using namespace hrl;
 using namespace hrl::scan;
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char *what) { return fail(HRL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
+constexpr char LIB[] = "hrl_scan";
 constexpr int MAX_BLOCK = 256;
 
 __global__ __launch_bounds__(MAX_BLOCK) void scan_kernel(const DevCfg *cfg, const float *state, const float *items, const int32_t *aux, const uint8_t *mask, float *range,
@@ -69,45 +61,6 @@ __global__ __launch_bounds__(MAX_BLOCK) void scan_kernel(const DevCfg *cfg, cons
     }
 }
 
-/* The kernel constants of every (device, config) this process has scanned, uploaded once and kept: a launch with a known config
- * allocates and copies nothing (graph capture).  Entries are never freed -- a captured graph may hold their address. */
-struct CacheEntry { int device; hrl_config cfg; DevCfg *d_dc; };
-std::mutex g_mutex;
-std::vector<CacheEntry> g_cache;
-constexpr size_t CACHE_MAX = 1024;
-
-int devcfg_for(const hrl_config *cfg, int device, DevCfg **out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    for (const CacheEntry &e : g_cache)
-        if (e.device == device && memcmp(&e.cfg, cfg, sizeof(hrl_config)) == 0) { *out = e.d_dc; return HRL_OK; }
-    if (g_cache.size() >= CACHE_MAX) return fail(HRL_ERR_BAD_ARG, "hrl_scan: more than 1024 distinct configs scanned by this process (their constants are kept for captured graphs)");
-    DevCfg dc, *d = nullptr;
-    build_devcfg(*cfg, dc);
-    hipError_t e = hipMalloc((void **)&d, sizeof(DevCfg));
-    if (e == hipSuccess) e = hipMemcpy(d, &dc, sizeof(DevCfg), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        return hip_fail(e, "hrl_scan: device constants (the first call with a config must happen outside stream capture)");
-    }
-    g_cache.push_back(CacheEntry{device, *cfg, d});
-    *out = d;
-    return HRL_OK;
-}
-
-/* the device guard of the step library (hrl_hip.hip: check_call): a launch goes to the CURRENT device, so the buffers must live there */
-int check_device(const void *p, const char *name, int cur) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(HRL_ERR_BAD_ARG, std::string("hrl_scan: ") + name + " is not memory the HIP runtime knows (device pointers are required)");
-    }
-    if (a.type == hipMemoryTypeDevice && a.device != cur)
-        return fail(HRL_ERR_BAD_ARG, std::string("hrl_scan: ") + name + " lives on HIP device " + std::to_string(a.device) + ", the current device is " + std::to_string(cur) +
-                                         ": hipSetDevice(" + std::to_string(a.device) + ") before calling");
-    return HRL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -121,33 +74,22 @@ int hrl_scan(const hrl_config *cfg, const hrl_buffers *b, const hrl_scan_spec *s
     std::string why = validate(cfg);
     if (why.empty()) why = validate_spec(spec);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_scan: " + why);
-    if (!b) return fail(HRL_ERR_BAD_ARG, "hrl_scan: null buffer record");
-    if (b->struct_size < HRL_BUFFERS_SIZE_V7_BASE || b->struct_size > 4096 || b->struct_size % sizeof(void *) != 0)
-        return fail(HRL_ERR_BAD_ARG, "hrl_scan: hrl_buffers.struct_size is not the size of a known layout: initialise the record with hrl_buffers_init() (include/hrl_envs.h)");
-    if (!b->state || !b->aux || !range || !hit) return fail(HRL_ERR_BAD_ARG, "hrl_scan: null state, aux, range or hit");
+    constexpr char NULLS[] = "hrl_scan: null state, aux, range or hit";
+    if (const int rc = check_record(LIB, b, NULLS)) return rc;
+    if (!range || !hit) return fail(HRL_ERR_BAD_ARG, NULLS);
     if (reinterpret_cast<uintptr_t>(range) % 4 != 0 || reinterpret_cast<uintptr_t>(hit) % 4 != 0) return fail(HRL_ERR_BAD_ARG, "hrl_scan: range and hit must be 4-byte aligned");
-    int ndev = 0, cur = -1;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HRL_ERR_NO_DEVICE, "hrl_scan: no HIP device (this library has no CPU path)");
-    }
-    if (hipGetDevice(&cur) != hipSuccess) return fail(HRL_ERR_HIP, "hrl_scan: hipGetDevice");
-    /* (a stream that is being captured: the pointers were looked at by the call that came before the capture) */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    if (cap == hipStreamCaptureStatusNone) {
-        if (const int rc = check_device(b->state, "state", cur)) return rc;
-        if (const int rc = check_device(range, "range", cur)) return rc;
-        if (const int rc = check_device(hit, "hit", cur)) return rc;
-    }
+    Context ctx;
+    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
+    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
+    if (const int rc = check_device(LIB, ctx, range, "range")) return rc;
+    if (const int rc = check_device(LIB, ctx, hit, "hit")) return rc;
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(cfg, cur, &d_dc)) return rc;
+    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
     const int waves = (spec->n_rays + 63) / 64; /* a 64-ray scan does not carry three idle waves */
     const int block = 64 * (waves < 4 ? waves : 4);
     hipLaunchKernelGGL(scan_kernel, dim3(cfg->num_envs), dim3(block), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, mask, range, hit, *spec);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HRL_OK : hip_fail(e, "hrl_scan launch");
+    return launched(LIB);
 }
 
 const char *hrl_scan_last_error(void) { return g_err.c_str(); }

@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _capi as K
-from ._lib import HrlError
+from . import _sensor
 from .render_device import HRL_VIEW_EGO, HRL_VIEW_EGO_HEADING, HRL_VIEW_WORLD, MODES, _mode  # noqa: F401  (the renderer's modes)
 from .scan_device import ALL, BOX, FOOD, POISON, TARGET, WALL  # noqa: F401  (the scanner's class bits)
 
@@ -30,47 +30,20 @@ FIELDS = (('dist', torch.float32), ('parent', torch.uint8))
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_FIELD_LIB') or os.path.join(_PKG, 'libhrl_field_hip.so')
 SYMBOLS = ['hrl_field_default_spec', 'hrl_field', 'hrl_field_last_error']   # every symbol include/hrl_field.h declares
-_lib = None
 
 
-class hrl_field_spec(C.Structure):
+class hrl_field_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('mode', C.c_int32), ('centre', C.c_float * 2),
                 ('half_extent', C.c_float), ('blocking', C.c_uint32), ('sources', C.c_uint32), ('margin', C.c_float)]
-
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        if 'struct_size' not in kw:
-            self.struct_size = C.sizeof(type(self))
-
-    def copy(self):
-        s = hrl_field_spec()
-        C.memmove(C.byref(s), C.byref(self), C.sizeof(hrl_field_spec))
-        return s
 
 
 class hrl_field_out(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HrlError(f'{LIB_PATH} is missing: build it with `python -m hrl_pybullet_envs_amd.build` '
-                           '(hipcc --offload-arch=gfx950); the batched navigation field has no CPU fallback')
-        L = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
-            getattr(L, s)
-        L.hrl_field_last_error.restype = C.c_char_p
-        L.hrl_field_default_spec.argtypes = [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_field_spec)]
-        L.hrl_field.argtypes = [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_field_spec), C.c_void_p, C.POINTER(hrl_field_out), C.c_void_p]
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    if rc != K.HRL_OK:
-        raise HrlError(f'hrl_field error {rc}: {lib().hrl_field_last_error().decode()}')
+lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_field', 'the batched navigation field has', {
+    'hrl_field_default_spec': [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_field_spec)],
+    'hrl_field': [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_field_spec), C.c_void_p, C.POINTER(hrl_field_out), C.c_void_p]})
 
 
 def default_spec(cfg, mode='world', width=64, height=64):
@@ -136,28 +109,14 @@ def cell_index(spec, state, xy):
 def field(cfg, bufs_ref, spec, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Field; a None one is not computed), each [N, height, width] on the current device, from the
     buffer record behind `bufs_ref`."""
-    o = hrl_field_out(**{name: (None if t is None else t.data_ptr()) for (name, _), t in zip(FIELDS, out)})
+    o = _sensor.out_record(hrl_field_out, FIELDS, out)
     check(lib().hrl_field(C.byref(cfg), bufs_ref, C.byref(spec), mask_ptr, C.byref(o), stream))
     return out
 
 
 def check_out(out, n, spec, device):
-    """`out=` of BatchedEnv.field(): a Field whose members are None (skipped) or contiguous [N, height, width] tensors of the member's
-    dtype on the env's device; at least one must be given."""
+    """`out=` of BatchedEnv.field(): a Field whose members are None (skipped) or contiguous, 4-byte aligned [N, height, width] tensors of the
+    member's dtype on the env's device; at least one must be given."""
     if not isinstance(out, Field):
         raise TypeError('out must be a field_device.Field (a None member is skipped)')
-    shape = (n, spec.height, spec.width)
-    for (name, dtype), t in zip(FIELDS, out):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-            raise TypeError(f'out.{name} must be a {dtype} tensor, got {getattr(t, "dtype", type(t))}')
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f'out.{name} must be contiguous {shape}, got {tuple(t.shape)}')
-        if t.device != device:
-            raise ValueError(f'out.{name} lives on {t.device}, the env on {device}')
-        if t.data_ptr() % 4:
-            raise ValueError(f'out.{name} must be 4-byte aligned')
-    if all(t is None for t in out):
-        raise ValueError('out holds no tensor: at least one output must be given')
-    return out
+    return _sensor.check_tensors(out, 'out.', FIELDS, (n, spec.height, spec.width), device, 4, optional=True)

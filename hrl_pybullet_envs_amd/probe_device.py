@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _capi as K
-from ._lib import HrlError
+from . import _sensor
 from .scan_device import ALL, BOX, FOOD, HIT_BOX, HIT_FOOD, HIT_NAMES, HIT_NONE, HIT_POISON, HIT_TARGET, HIT_WALL, POISON, TARGET, WALL, decode  # noqa: F401  (the scanner's classes and codes)
 
 HRL_PROBE_WORLD, HRL_PROBE_EGO, HRL_PROBE_HEADING = 0, 1, 2
@@ -28,46 +28,19 @@ FIELDS = (('clearance', torch.float32), ('nearest', torch.int32), ('sight', torc
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_PROBE_LIB') or os.path.join(_PKG, 'libhrl_probe_hip.so')
 SYMBOLS = ['hrl_probe_default_spec', 'hrl_probe', 'hrl_probe_last_error']   # every symbol include/hrl_probe.h declares
-_lib = None
 
 
-class hrl_probe_spec(C.Structure):
+class hrl_probe_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('n_points', C.c_int32), ('frame', C.c_int32), ('classes', C.c_uint32), ('margin', C.c_float)]
-
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        if 'struct_size' not in kw:
-            self.struct_size = C.sizeof(type(self))
-
-    def copy(self):
-        s = hrl_probe_spec()
-        C.memmove(C.byref(s), C.byref(self), C.sizeof(hrl_probe_spec))
-        return s
 
 
 class hrl_probe_out(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HrlError(f'{LIB_PATH} is missing: build it with `python -m hrl_pybullet_envs_amd.build` '
-                           '(hipcc --offload-arch=gfx950); the batched point probes have no CPU fallback')
-        L = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
-            getattr(L, s)
-        L.hrl_probe_last_error.restype = C.c_char_p
-        L.hrl_probe_default_spec.argtypes = [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_probe_spec)]
-        L.hrl_probe.argtypes = [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_probe_spec), C.c_void_p, C.c_void_p, C.POINTER(hrl_probe_out), C.c_void_p]
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    if rc != K.HRL_OK:
-        raise HrlError(f'hrl_probe error {rc}: {lib().hrl_probe_last_error().decode()}')
+lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_probe', 'the batched point probes have', {
+    'hrl_probe_default_spec': [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_probe_spec)],
+    'hrl_probe': [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_probe_spec), C.c_void_p, C.c_void_p, C.POINTER(hrl_probe_out), C.c_void_p]})
 
 
 def _frame(frame):
@@ -103,7 +76,7 @@ def corner_table(cfg, margin):
 def probe(cfg, bufs_ref, spec, points, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Probe; None fields are not computed), each [N, n_points] on the current device, from the
     buffer record behind `bufs_ref` and `points` float32 [N, n_points, 2]."""
-    o = hrl_probe_out(**{name: (None if t is None else t.data_ptr()) for (name, _), t in zip(FIELDS, out)})
+    o = _sensor.out_record(hrl_probe_out, FIELDS, out)
     check(lib().hrl_probe(C.byref(cfg), bufs_ref, C.byref(spec), points.data_ptr(), mask_ptr, C.byref(o), stream))
     return out
 
@@ -120,20 +93,8 @@ def check_points(points, n, device):
 
 
 def check_out(out, n, spec, device):
-    """`out=` of BatchedEnv.probe(): a Probe whose fields are None (skipped) or contiguous [N, n_points] tensors of the field's dtype on the
-    env's device; at least one must be given."""
+    """`out=` of BatchedEnv.probe(): a Probe whose fields are None (skipped) or contiguous, 4-byte aligned [N, n_points] tensors of the field's dtype
+    on the env's device; at least one must be given."""
     if not isinstance(out, Probe):
         raise TypeError('out must be a probe_device.Probe (None fields are skipped)')
-    shape = (n, spec.n_points)
-    for (name, dtype), t in zip(FIELDS, out):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-            raise TypeError(f'out.{name} must be a {dtype} tensor, got {getattr(t, "dtype", type(t))}')
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f'out.{name} must be contiguous {shape}, got {tuple(t.shape)}')
-        if t.device != device:
-            raise ValueError(f'out.{name} lives on {t.device}, the env on {device}')
-    if all(t is None for t in out):
-        raise ValueError('out holds no tensor: at least one output must be given')
-    return out
+    return _sensor.check_tensors(out, 'out.', FIELDS, (n, spec.n_points), device, 4, optional=True)

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import _capi as K
-from ._lib import HrlError
+from . import _sensor
 
 HRL_VIEW_WORLD, HRL_VIEW_EGO, HRL_VIEW_EGO_HEADING = 0, 1, 2
 MODES = {'world': HRL_VIEW_WORLD, 'ego': HRL_VIEW_EGO, 'ego_heading': HRL_VIEW_EGO_HEADING}
@@ -22,43 +22,16 @@ PALETTE = {'ground': (240, 240, 240), 'wall': (60, 60, 60), 'box': (170, 170, 17
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_RENDER_LIB') or os.path.join(_PKG, 'libhrl_render_hip.so')
 SYMBOLS = ['hrl_render_default_view', 'hrl_render', 'hrl_render_last_error']   # every symbol include/hrl_render.h declares
-_lib = None
 
 
-class hrl_view(C.Structure):
+class hrl_view(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('mode', C.c_int32),
                 ('centre', C.c_float * 2), ('half_extent', C.c_float)]
 
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        if 'struct_size' not in kw:
-            self.struct_size = C.sizeof(type(self))
 
-    def copy(self):
-        v = hrl_view()
-        C.memmove(C.byref(v), C.byref(self), C.sizeof(hrl_view))
-        return v
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HrlError(f'{LIB_PATH} is missing: build it with `python -m hrl_pybullet_envs_amd.build` '
-                           '(hipcc --offload-arch=gfx950); the batched renderer has no CPU fallback')
-        L = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
-            getattr(L, s)
-        L.hrl_render_last_error.restype = C.c_char_p
-        L.hrl_render_default_view.argtypes = [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_view)]
-        L.hrl_render.argtypes = [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_view), C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    if rc != K.HRL_OK:
-        raise HrlError(f'hrl_render error {rc}: {lib().hrl_render_last_error().decode()}')
+lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_render', 'the batched renderer has', {
+    'hrl_render_default_view': [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_view)],
+    'hrl_render': [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_view), C.c_void_p, C.c_void_p, C.c_void_p]})
 
 
 def _mode(mode):
@@ -88,13 +61,4 @@ def render(cfg, bufs_ref, view, mask_ptr, out, stream):
 
 def check_out(out, n, view, device):
     """`out=` of BatchedEnv.render(): uint8 [N, H, W, 3], contiguous, 16-byte aligned, on the env's device."""
-    shape = (n, view.height, view.width, 3)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8:
-        raise TypeError(f'out must be a torch.uint8 tensor, got {getattr(out, "dtype", type(out))}')
-    if tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f'out must be contiguous {shape}, got {tuple(out.shape)}')
-    if out.device != device:
-        raise ValueError(f'out lives on {out.device}, the env on {device}')
-    if out.data_ptr() % 16:
-        raise ValueError('out must be 16-byte aligned')
-    return out
+    return _sensor.check_tensors((out,), 'out', (('', torch.uint8),), (n, view.height, view.width, 3), device, 16)[0]

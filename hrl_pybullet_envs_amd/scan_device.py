@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _capi as K
-from ._lib import HrlError
+from . import _sensor
 
 HRL_SCAN_WORLD, HRL_SCAN_HEADING = 0, 1
 FRAMES = {'world': HRL_SCAN_WORLD, 'heading': HRL_SCAN_HEADING}
@@ -19,47 +19,21 @@ MAX_RAYS = 512
 WALL, BOX, FOOD, POISON, TARGET, ALL = 1, 2, 4, 8, 16, 31                      # hrl_scan_spec.classes
 HIT_NONE, HIT_WALL, HIT_BOX, HIT_FOOD, HIT_POISON, HIT_TARGET = range(6)       # the low byte of `hit`
 HIT_NAMES = ('none', 'wall', 'box', 'food', 'poison', 'target')
+FIELDS = (('range', torch.float32), ('hit', torch.int32))                         # the two outputs
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_SCAN_LIB') or os.path.join(_PKG, 'libhrl_scan_hip.so')
 SYMBOLS = ['hrl_scan_default_spec', 'hrl_scan', 'hrl_scan_last_error']   # every symbol include/hrl_scan.h declares
-_lib = None
 
 
-class hrl_scan_spec(C.Structure):
+class hrl_scan_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('n_rays', C.c_int32), ('frame', C.c_int32), ('first_angle', C.c_float), ('step_angle', C.c_float),
                 ('max_range', C.c_float), ('classes', C.c_uint32)]
 
-    def __init__(self, **kw):
-        super().__init__(**kw)
-        if 'struct_size' not in kw:
-            self.struct_size = C.sizeof(type(self))
 
-    def copy(self):
-        s = hrl_scan_spec()
-        C.memmove(C.byref(s), C.byref(self), C.sizeof(hrl_scan_spec))
-        return s
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HrlError(f'{LIB_PATH} is missing: build it with `python -m hrl_pybullet_envs_amd.build` '
-                           '(hipcc --offload-arch=gfx950); the batched range scanner has no CPU fallback')
-        L = C.CDLL(LIB_PATH)
-        for s in SYMBOLS:
-            getattr(L, s)
-        L.hrl_scan_last_error.restype = C.c_char_p
-        L.hrl_scan_default_spec.argtypes = [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_scan_spec)]
-        L.hrl_scan.argtypes = [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_scan_spec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    if rc != K.HRL_OK:
-        raise HrlError(f'hrl_scan error {rc}: {lib().hrl_scan_last_error().decode()}')
+lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_scan', 'the batched range scanner has', {
+    'hrl_scan_default_spec': [C.POINTER(K.hrl_config), C.c_int32, C.POINTER(hrl_scan_spec)],
+    'hrl_scan': [C.POINTER(K.hrl_config), C.c_void_p, C.POINTER(hrl_scan_spec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]})
 
 
 def _frame(frame):
@@ -104,15 +78,8 @@ def scan(cfg, bufs_ref, spec, mask_ptr, rng, hit, stream):
 
 
 def check_out(out, n, spec, device):
-    """`out=` of BatchedEnv.scan(): (range float32, hit int32), each contiguous [N, n_rays] on the env's device."""
+    """`out=` of BatchedEnv.scan(): (range float32, hit int32), each contiguous [N, n_rays], 4-byte aligned, on the env's device."""
     if not isinstance(out, (tuple, list)) or len(out) != 2:
         raise TypeError('out must be a pair (range, hit)')
-    shape = (n, spec.n_rays)
-    for t, dtype, name in ((out[0], torch.float32, 'range'), (out[1], torch.int32, 'hit')):
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-            raise TypeError(f'out {name} must be a {dtype} tensor, got {getattr(t, "dtype", type(t))}')
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f'out {name} must be contiguous {shape}, got {tuple(t.shape)}')
-        if t.device != device:
-            raise ValueError(f'out {name} lives on {t.device}, the env on {device}')
+    _sensor.check_tensors(out, 'out ', FIELDS, (n, spec.n_rays), device, 4)
     return out[0], out[1]

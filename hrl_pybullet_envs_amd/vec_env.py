@@ -141,6 +141,28 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
+    # the sensors (render, scan, probe, field): each is one launch of a library of its own on the state / items / aux tensors as they are
+    def _default_spec(self, key, make):
+        """The spec a sensor uses when none is given: asked of its library once per `key`."""
+        specs = self.__dict__.setdefault('_default_specs', {})
+        if key not in specs:
+            specs[key] = make()
+        return specs[key]
+
+    def _fresh(self, mask, shape, dtype):
+        """A new output tensor [N, *shape]: zeros where a mask may leave envs unwritten."""
+        return (torch.empty if mask is None else torch.zeros)(self.num_envs, *shape, dtype=dtype, device=self.device)
+
+    def _sensor_launch(self, keep, mask, launch):
+        """launch(mask pointer or None, stream) on this env's device and the current stream; the converted mask stays alive as attribute `keep`."""
+        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        if torch.cuda.current_device() == self.device.index:   # as in step(): the context manager costs more host time than this helper does
+            launch(None if m is None else m.data_ptr(), self._stream())
+        else:
+            with torch.cuda.device(self.device):
+                launch(None if m is None else m.data_ptr(), self._stream())
+        setattr(self, keep, m)  # until the stream has consumed it
+
     def render(self, view=None, mask=None, out=None):
         """A top-down RGB image of every env: torch.uint8 [N, H, W, 3] on this device, from ONE launch on the current stream (render_device.py,
         include/hrl_render.h) -- what a high-level policy's CNN or a video writer reads without leaving HBM.  `view`: an hrl_view
@@ -149,18 +171,12 @@ class BatchedEnv:
         the state / items / aux tensors as they are; nothing else is read or written.  Capturable: call it once before the capture."""
         from . import render_device as R
         if view is None:
-            view = getattr(self, '_default_view', None)
-            if view is None:
-                view = self._default_view = R.default_view(self.cfg)
+            view = self._default_spec('render', lambda: R.default_view(self.cfg))
         if out is None:
-            make = torch.empty if mask is None else torch.zeros
-            out = make(self.num_envs, view.height, view.width, 3, dtype=torch.uint8, device=self.device)
+            out = self._fresh(mask, (view.height, view.width, 3), torch.uint8)
         else:
             R.check_out(out, self.num_envs, view, self.device)
-        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            R.render(self.cfg, self._bufs_ref, view, None if m is None else m.data_ptr(), out, self._stream())
-        self._last_render_mask = m  # keep alive until the stream has consumed it
+        self._sensor_launch('_last_render_mask', mask, lambda m, stream: R.render(self.cfg, self._bufs_ref, view, m, out, stream))
         return out
 
     def scan(self, spec=None, mask=None, out=None):
@@ -172,21 +188,14 @@ class BatchedEnv:
         items / aux tensors as they are; nothing else is read or written.  Capturable: call it once before the capture."""
         from . import scan_device as S
         if spec is None:
-            spec = getattr(self, '_default_scan', None)
-            if spec is None:
-                spec = self._default_scan = S.default_spec(self.cfg)
+            spec = self._default_spec('scan', lambda: S.default_spec(self.cfg))
         if out is None:
             if not 1 <= spec.n_rays <= S.MAX_RAYS:   # (the library refuses it too; no tensor can be shaped after it)
                 raise ValueError(f'spec.n_rays must be within 1..{S.MAX_RAYS}, got {spec.n_rays}')
-            make = torch.empty if mask is None else torch.zeros
-            rng = make(self.num_envs, spec.n_rays, dtype=torch.float32, device=self.device)
-            hit = make(self.num_envs, spec.n_rays, dtype=torch.int32, device=self.device)
+            rng, hit = self._fresh(mask, (spec.n_rays,), torch.float32), self._fresh(mask, (spec.n_rays,), torch.int32)
         else:
             rng, hit = S.check_out(out, self.num_envs, spec, self.device)
-        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            S.scan(self.cfg, self._bufs_ref, spec, None if m is None else m.data_ptr(), rng, hit, self._stream())
-        self._last_scan_mask = m  # keep alive until the stream has consumed it
+        self._sensor_launch('_last_scan_mask', mask, lambda m, stream: S.scan(self.cfg, self._bufs_ref, spec, m, rng, hit, stream))
         return rng, hit
 
     def probe(self, points, spec=None, mask=None, out=None):
@@ -202,20 +211,14 @@ class BatchedEnv:
         from . import probe_device as P
         points = P.check_points(points, self.num_envs, self.device)
         if spec is None:
-            spec = getattr(self, '_default_probe', None)
-            if spec is None or spec.n_points != points.shape[1]:
-                spec = self._default_probe = P.default_spec(self.cfg, 'world', points.shape[1])
+            spec = self._default_spec(('probe', points.shape[1]), lambda: P.default_spec(self.cfg, 'world', points.shape[1]))
         elif spec.n_points != points.shape[1]:
             raise ValueError(f'spec.n_points is {spec.n_points}, points hold {points.shape[1]} per env')
         if out is None:
-            make = torch.empty if mask is None else torch.zeros
-            out = P.Probe(*(make(self.num_envs, spec.n_points, dtype=dtype, device=self.device) for _, dtype in P.FIELDS))
+            out = P.Probe(*(self._fresh(mask, (spec.n_points,), dtype) for _, dtype in P.FIELDS))
         else:
             P.check_out(out, self.num_envs, spec, self.device)
-        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            P.probe(self.cfg, self._bufs_ref, spec, points, None if m is None else m.data_ptr(), out, self._stream())
-        self._last_probe_mask = m  # keep alive until the stream has consumed it
+        self._sensor_launch('_last_probe_mask', mask, lambda m, stream: P.probe(self.cfg, self._bufs_ref, spec, points, m, out, stream))
         return out
 
     def field(self, spec=None, mask=None, out=None):
@@ -230,20 +233,14 @@ class BatchedEnv:
         Capturable: call it once before the capture."""
         from . import field_device as F
         if spec is None:
-            spec = getattr(self, '_default_field', None)
-            if spec is None:
-                spec = self._default_field = F.default_spec(self.cfg)
+            spec = self._default_spec('field', lambda: F.default_spec(self.cfg))
         if out is None:
             if not (F.MIN_SIZE <= spec.width <= F.MAX_SIZE and F.MIN_SIZE <= spec.height <= F.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
                 raise ValueError(f'spec.width and spec.height must be within {F.MIN_SIZE}..{F.MAX_SIZE}, got {spec.width} x {spec.height}')
-            make = torch.empty if mask is None else torch.zeros
-            out = F.Field(*(make(self.num_envs, spec.height, spec.width, dtype=dtype, device=self.device) for _, dtype in F.FIELDS))
+            out = F.Field(*(self._fresh(mask, (spec.height, spec.width), dtype) for _, dtype in F.FIELDS))
         else:
             F.check_out(out, self.num_envs, spec, self.device)
-        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            F.field(self.cfg, self._bufs_ref, spec, None if m is None else m.data_ptr(), out, self._stream())
-        self._last_field_mask = m  # keep alive until the stream has consumed it
+        self._sensor_launch('_last_field_mask', mask, lambda m, stream: F.field(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
     def close(self):

@@ -1,16 +1,7 @@
-/* Stand-alone program, built with -fsanitize=address,undefined: computes every case of check_cases.h and prints sizeof(hrl_field_spec)
- * and a checksum per case.  Exit status 0 = every launch succeeded and the sanitisers saw nothing. */
+/* Stand-alone program, built with -fsanitize=address,undefined: computes every case of check_cases.h (../check_main.h). */
 #include "check_cases.h"
+#include "../check_main.h"
 
 extern "C" unsigned long long field_sizeof_spec(void);
 
-int main() {
-    printf("sizeof_hrl_field_spec %llu\n", field_sizeof_spec());
-    for (int k = 0; k < field_check::n_cases(); ++k) {
-        char name[64];
-        uint64_t sum = 0;
-        if (field_check::run_case(k, name, sizeof name, &sum) != HRL_OK) return 1;
-        printf("case %s %016llx\n", name, (unsigned long long)sum);
-    }
-    return 0;
-}
+int main() { return check_main("hrl_field_spec", field_sizeof_spec(), field_check::n_cases(), field_check::run_case); }

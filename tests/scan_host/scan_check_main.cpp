@@ -1,16 +1,7 @@
-/* Stand-alone program, built with -fsanitize=address,undefined: scans every case of check_cases.h and prints sizeof(hrl_scan_spec)
- * and a checksum per case.  Exit status 0 = every scan succeeded and the sanitisers saw nothing. */
+/* Stand-alone program, built with -fsanitize=address,undefined: scans every case of check_cases.h (../check_main.h). */
 #include "check_cases.h"
+#include "../check_main.h"
 
 extern "C" unsigned long long scan_sizeof_spec(void);
 
-int main() {
-    printf("sizeof_hrl_scan_spec %llu\n", scan_sizeof_spec());
-    for (int k = 0; k < scan_check::n_cases(); ++k) {
-        char name[64];
-        uint64_t sum = 0;
-        if (scan_check::run_case(k, name, sizeof name, &sum) != HRL_OK) return 1;
-        printf("case %s %016llx\n", name, (unsigned long long)sum);
-    }
-    return 0;
-}
+int main() { return check_main("hrl_scan_spec", scan_sizeof_spec(), scan_check::n_cases(), scan_check::run_case); }
