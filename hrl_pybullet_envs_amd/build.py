@@ -1,7 +1,8 @@
 """Build the gfx950 HIP libraries in-tree: hrl_pybullet_envs_amd/libhrl_envs_hip.so (the step, include/hrl_envs.h),
 hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h), hrl_pybullet_envs_amd/libhrl_scan_hip.so
 (the batched range scanner, include/hrl_scan.h), hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
-include/hrl_probe.h) and hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h).
+include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h) and
+hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -20,6 +21,8 @@ SENSORS = [('render', 'libhrl_render_hip.so', 'render_hip.hip', 'render_core.h',
            ('scan', 'libhrl_scan_hip.so', 'scan_hip.hip', 'scan_core.h', 'hrl_scan.h'),
            ('probe', 'libhrl_probe_hip.so', 'probe_hip.hip', 'probe_core.h', 'hrl_probe.h'),
            ('field', 'libhrl_field_hip.so', 'field_hip.hip', 'field_core.h', 'hrl_field.h')]
+# The routes stand on the field's whole chain and are an entry of their own, in the table's form: SENSORS stays the four sensors.
+ROUTE = ('route', 'libhrl_route_hip.so', 'route_hip.hip', 'route_core.h', 'hrl_route.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -79,16 +82,27 @@ def build_field(force=False, verbose=False):
     return build_sensor('field', force, verbose)
 
 
+def build_route(force=False, verbose=False):
+    """The route library; returns its path.  It depends on everything the field depends on plus its own three files."""
+    _, lib, source, core, header = ROUTE
+    lib = os.path.join(PKG, lib)
+    sources = [source, core, 'sensor_launch.h'] + [c for *_, c, _ in SENSORS] + SOURCES[1:]
+    if force or _stale(lib, sources, ['hrl_envs.h', header] + [h for *_, h in SENSORS]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The five libraries; returns the step library's path."""
+    """The six libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
         build_sensor(name, force, verbose)
+    build_route(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS:
+    for _, lib, *_ in SENSORS + [ROUTE]:
         print(os.path.join(PKG, lib))

@@ -1,9 +1,9 @@
 /*
- * sensor_launch.h -- the host side that the sensor libraries share (render_hip.hip, scan_hip.hip, probe_hip.hip, field_hip.hip): the error
+ * sensor_launch.h -- the host side that the sensor libraries share (render_hip.hip, scan_hip.hip, probe_hip.hip, field_hip.hip, route_hip.hip): the error
  * string, the guards of the buffer record and of the pointers' devices, the cache of kernel constants and the launch epilogue.  Host only;
  * `lib` is the library's name as its messages carry it ("hrl_scan").
  *
- * Everything here has INTERNAL linkage (one unnamed namespace, no inline or template statics): the four libraries are loaded into one
+ * Everything here has INTERNAL linkage (one unnamed namespace, no inline or template statics): the libraries are loaded into one
  * process, and the dynamic loader may unify a symbol of vague linkage across them -- hrl_scan_last_error() would answer with the
  * renderer's message.  Each library therefore holds its own copy of the state below.
  */

@@ -217,6 +217,12 @@ class BatchedGymEnv:
         the grid of render_batch() (BatchedEnv.field; field_device.default_spec for other grids, obstacles and sources)."""
         return self._backend().field(spec, mask, out)
 
+    def route_batch(self, starts=None, spec=None, mask=None, out=None):
+        """Routes for EVERY env in one launch: Route(waypoints [N, P, K, 2], count [N, P], length [N, P], cells [N, P, K]) on the env's
+        device, from `starts` float32 [N, P, 2] (None: the robot) down the field of field_batch() to the nearest source, pulled tight
+        into waypoints (BatchedEnv.route; route_device.default_spec for other grids, frames and numbers of waypoints)."""
+        return self._backend().route(starts, spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

@@ -141,7 +141,7 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
-    # the sensors (render, scan, probe, field): each is one launch of a library of its own on the state / items / aux tensors as they are
+    # the sensors (render, scan, probe, field, route): each is one launch of a library of its own on the state / items / aux tensors as they are
     def _default_spec(self, key, make):
         """The spec a sensor uses when none is given: asked of its library once per `key`."""
         specs = self.__dict__.setdefault('_default_specs', {})
@@ -241,6 +241,34 @@ class BatchedEnv:
         else:
             F.check_out(out, self.num_envs, spec, self.device)
         self._sensor_launch('_last_field_mask', mask, lambda m, stream: F.field(self.cfg, self._bufs_ref, spec, m, out, stream))
+        return out
+
+    def route(self, starts=None, spec=None, mask=None, out=None):
+        """Routes down the navigation field: for P start points per env (`starts` float32 [N, P, 2] on this device, 1 <= P <= 64; None =
+        the robot's own place) a namedtuple Route(waypoints float32 [N, P, K, 2], count int32 [N, P], length float32 [N, P], cells int32
+        [N, P, K]) on this device, from ONE launch on the current stream (route_device.py, include/hrl_route.h).  The route follows the
+        field of the spec's field part from the start's cell to the nearest source and is pulled tight: a waypoint is kept only where the
+        straight line from the last one would touch a blocked cell.  waypoints = the world x, y of the kept cells' centres, cells = row *
+        width + column of them, both padded with the last one up to K = spec.max_waypoints; count = how many the whole route has (it may
+        exceed K; 0 = there is no route: the start is outside the grid, not finite, or on a blocked or cut-off cell, and then length is
+        +inf, cells -1 and waypoints NaN); length = the polyline's length in metres.  `spec`: an hrl_route_spec
+        (route_device.default_spec(cfg, mode, width, height, frame, n_starts, max_waypoints)); None = the default field, starts as
+        offsets from the robot, 16 waypoints.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh tensors).  `out`: a Route of
+        tensors to reuse; a None member is not computed.  The routes are of the state / items / aux tensors as they are; nothing else is
+        read or written.  Capturable: call it once before the capture."""
+        from . import route_device as R
+        p = 1 if starts is None else R.check_starts(starts, self.num_envs, self.device).shape[1]
+        if spec is None:
+            spec = self._default_spec(('route', p), lambda: R.default_spec(self.cfg, n_starts=p))
+        elif spec.n_starts != p:
+            raise ValueError(f'spec.n_starts is {spec.n_starts}, starts hold {p} per env' if starts is not None else f'spec.n_starts is {spec.n_starts}: without starts there is one per env, the robot')
+        if out is None:
+            if not R.MIN_WAYPOINTS <= spec.max_waypoints <= R.MAX_WAYPOINTS:   # (the library refuses it too; no tensor can be shaped after it)
+                raise ValueError(f'spec.max_waypoints must be within {R.MIN_WAYPOINTS}..{R.MAX_WAYPOINTS}, got {spec.max_waypoints}')
+            out = R.Route(*(self._fresh(mask, shape, dtype) for shape, (_, dtype) in zip(R.shapes(spec), R.FIELDS)))
+        else:
+            R.check_out(out, self.num_envs, spec, self.device)
+        self._sensor_launch('_last_route_mask', mask, lambda m, stream: R.route(self.cfg, self._bufs_ref, spec, starts, m, out, stream))
         return out
 
     def close(self):
