@@ -1,8 +1,9 @@
 """Build the gfx950 HIP libraries in-tree: hrl_pybullet_envs_amd/libhrl_envs_hip.so (the step, include/hrl_envs.h),
 hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h), hrl_pybullet_envs_amd/libhrl_scan_hip.so
 (the batched range scanner, include/hrl_scan.h), hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
-include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h) and
-hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h).
+include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h),
+hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h) and hrl_pybullet_envs_amd/libhrl_see_hip.so (the
+batched visibility map, include/hrl_see.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -23,6 +24,8 @@ SENSORS = [('render', 'libhrl_render_hip.so', 'render_hip.hip', 'render_core.h',
            ('field', 'libhrl_field_hip.so', 'field_hip.hip', 'field_core.h', 'hrl_field.h')]
 # The routes stand on the field's whole chain and are an entry of their own, in the table's form: SENSORS stays the four sensors.
 ROUTE = ('route', 'libhrl_route_hip.so', 'route_hip.hip', 'route_core.h', 'hrl_route.h')
+# The visibility map stands on the field's whole chain too (not on the routes), likewise as an entry of its own.
+SEE = ('see', 'libhrl_see_hip.so', 'see_hip.hip', 'see_core.h', 'hrl_see.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -82,9 +85,8 @@ def build_field(force=False, verbose=False):
     return build_sensor('field', force, verbose)
 
 
-def build_route(force=False, verbose=False):
-    """The route library; returns its path.  It depends on everything the field depends on plus its own three files."""
-    _, lib, source, core, header = ROUTE
+def _build_on_the_field(entry, force, verbose):
+    _, lib, source, core, header = entry
     lib = os.path.join(PKG, lib)
     sources = [source, core, 'sensor_launch.h'] + [c for *_, c, _ in SENSORS] + SOURCES[1:]
     if force or _stale(lib, sources, ['hrl_envs.h', header] + [h for *_, h in SENSORS]):
@@ -92,17 +94,28 @@ def build_route(force=False, verbose=False):
     return lib
 
 
+def build_route(force=False, verbose=False):
+    """The route library; returns its path.  It depends on everything the field depends on plus its own three files."""
+    return _build_on_the_field(ROUTE, force, verbose)
+
+
+def build_see(force=False, verbose=False):
+    """The visibility map's library; returns its path.  It depends on everything the field depends on plus its own three files."""
+    return _build_on_the_field(SEE, force, verbose)
+
+
 def build(force=False, verbose=False):
-    """The six libraries; returns the step library's path."""
+    """The seven libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
         build_sensor(name, force, verbose)
     build_route(force, verbose)
+    build_see(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE]:
         print(os.path.join(PKG, lib))

@@ -223,6 +223,13 @@ class BatchedGymEnv:
         into waypoints (BatchedEnv.route; route_device.default_spec for other grids, frames and numbers of waypoints)."""
         return self._backend().route(starts, spec, mask, out)
 
+    def see_batch(self, spec=None, clear=None, mask=None, out=None):
+        """The visibility map of EVERY env in one launch: See(visible uint8 [N, H, W], seen uint8 [N, H, W], fresh int32 [N]) on the env's
+        device and on the grid of render_batch() and field_batch(): which cells the robot sees now, which it has seen this episode (a
+        memory the caller holds, see_device.memory) and how many are new (BatchedEnv.see; see_device.default_spec for other grids,
+        occluders, ranges and fields of view)."""
+        return self._backend().see(spec, clear, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

@@ -141,7 +141,7 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
-    # the sensors (render, scan, probe, field, route): each is one launch of a library of its own on the state / items / aux tensors as they are
+    # the sensors (render, scan, probe, field, route, see): each is one launch of a library of its own on the state / items / aux tensors as they are
     def _default_spec(self, key, make):
         """The spec a sensor uses when none is given: asked of its library once per `key`."""
         specs = self.__dict__.setdefault('_default_specs', {})
@@ -269,6 +269,34 @@ class BatchedEnv:
         else:
             R.check_out(out, self.num_envs, spec, self.device)
         self._sensor_launch('_last_route_mask', mask, lambda m, stream: R.route(self.cfg, self._bufs_ref, spec, starts, m, out, stream))
+        return out
+
+    def see(self, spec=None, clear=None, mask=None, out=None):
+        """The visibility map of every env: a namedtuple See(visible uint8 [N, H, W], seen uint8 [N, H, W], fresh int32 [N]) on this device,
+        from ONE launch on the current stream (see_device.py, include/hrl_see.h).  On the field's and the renderer's grid: visible = 1 where
+        the robot sees the cell's centre -- within spec.max_range, within the field of view spec.fov_cos about its heading, and with no
+        shape of spec.occluders before it (the probe's `blocker` test; spec.slack metres behind a surface still count, so the face of a
+        wall is lit).  `seen` is the episode's memory, HELD BY THE CALLER (see_device.memory): it is read and written as seen | visible,
+        in the world mode only, and `fresh` counts the cells seen for the first time.  `clear`: [N], envs whose memory starts from nothing
+        in this call (the step's `done`).  `spec`: an hrl_see_spec (see_device.default_spec(cfg, mode, width, height, fov_degrees,
+        max_range, slack)); None = the 64 x 64 world grid, WALL | BOX occlude, all round, a slack of one cell.  Envs with mask[i] == 0 keep
+        every byte.  `out`: a See of tensors to use; a None member is not computed; None = See(visible, None, None) in a fresh tensor.
+        The map is of the state / items / aux tensors as they are; nothing else is read or written.  Capturable: call it once before the
+        capture."""
+        from . import see_device as V
+        if spec is None:
+            spec = self._default_spec('see', lambda: V.default_spec(self.cfg))
+        if out is None:
+            if not (V.MIN_SIZE <= spec.width <= V.MAX_SIZE and V.MIN_SIZE <= spec.height <= V.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
+                raise ValueError(f'spec.width and spec.height must be within {V.MIN_SIZE}..{V.MAX_SIZE}, got {spec.width} x {spec.height}')
+            out = V.See(self._fresh(mask, (spec.height, spec.width), torch.uint8), None, None)
+        else:
+            V.check_out(out, self.num_envs, spec, self.device)
+        c = None if clear is None else clear.to(device=self.device, dtype=torch.uint8).contiguous()
+        if c is not None and tuple(c.shape) != (self.num_envs,):
+            raise ValueError(f'clear must be [{self.num_envs}], got {tuple(c.shape)}')
+        self._sensor_launch('_last_see_mask', mask, lambda m, stream: V.see(self.cfg, self._bufs_ref, spec, None if c is None else c.data_ptr(), m, out, stream))
+        self._last_see_clear = c  # until the stream has consumed it
         return out
 
     def close(self):

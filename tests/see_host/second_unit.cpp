@@ -1,0 +1,11 @@
+/* A second translation unit that includes the specification: step_core.h, host_cfg.h, render_core.h, scan_core.h, probe_core.h,
+ * field_core.h and see_core.h are headers of inline functions, so two units that include them must link into one library / program. */
+#include "../../hrl_pybullet_envs_amd/csrc/see_core.h"
+
+extern "C" unsigned long long see_sizeof_spec(void) { return sizeof(hrl_see_spec); }
+extern "C" unsigned long long see_sizeof_out(void) { return sizeof(hrl_see_out); }
+extern "C" const char *see_validate_spec(const hrl_see_spec *s) {
+    static thread_local std::string why;
+    why = hrl::see::validate_spec(s);
+    return why.c_str();
+}
