@@ -2,8 +2,9 @@
 hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_render.h), hrl_pybullet_envs_amd/libhrl_scan_hip.so
 (the batched range scanner, include/hrl_scan.h), hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
 include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h),
-hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h) and hrl_pybullet_envs_amd/libhrl_see_hip.so (the
-batched visibility map, include/hrl_see.h).
+hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h), hrl_pybullet_envs_amd/libhrl_see_hip.so (the
+batched visibility map, include/hrl_see.h) and hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map,
+include/hrl_frontier.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -26,6 +27,8 @@ SENSORS = [('render', 'libhrl_render_hip.so', 'render_hip.hip', 'render_core.h',
 ROUTE = ('route', 'libhrl_route_hip.so', 'route_hip.hip', 'route_core.h', 'hrl_route.h')
 # The visibility map stands on the field's whole chain too (not on the routes), likewise as an entry of its own.
 SEE = ('see', 'libhrl_see_hip.so', 'see_hip.hip', 'see_core.h', 'hrl_see.h')
+# The frontier map stands on the field's chain and on the routes' specification (the test that names a point's cell, the cell-to-world function).
+FRONTIER = ('frontier', 'libhrl_frontier_hip.so', 'frontier_hip.hip', 'frontier_core.h', 'hrl_frontier.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -85,11 +88,11 @@ def build_field(force=False, verbose=False):
     return build_sensor('field', force, verbose)
 
 
-def _build_on_the_field(entry, force, verbose):
+def _build_on_the_field(entry, force, verbose, more_sources=(), more_headers=()):
     _, lib, source, core, header = entry
     lib = os.path.join(PKG, lib)
-    sources = [source, core, 'sensor_launch.h'] + [c for *_, c, _ in SENSORS] + SOURCES[1:]
-    if force or _stale(lib, sources, ['hrl_envs.h', header] + [h for *_, h in SENSORS]):
+    sources = [source, core, 'sensor_launch.h'] + list(more_sources) + [c for *_, c, _ in SENSORS] + SOURCES[1:]
+    if force or _stale(lib, sources, ['hrl_envs.h', header] + list(more_headers) + [h for *_, h in SENSORS]):
         _compile(lib, source, verbose)
     return lib
 
@@ -104,18 +107,25 @@ def build_see(force=False, verbose=False):
     return _build_on_the_field(SEE, force, verbose)
 
 
+def build_frontier(force=False, verbose=False):
+    """The frontier map's library; returns its path.  It depends on everything the field depends on, on the routes' specification and
+    header, and on its own three files."""
+    return _build_on_the_field(FRONTIER, force, verbose, (ROUTE[3],), (ROUTE[4],))
+
+
 def build(force=False, verbose=False):
-    """The seven libraries; returns the step library's path."""
+    """The eight libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
         build_sensor(name, force, verbose)
     build_route(force, verbose)
     build_see(force, verbose)
+    build_frontier(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER]:
         print(os.path.join(PKG, lib))

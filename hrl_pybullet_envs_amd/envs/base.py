@@ -230,6 +230,13 @@ class BatchedGymEnv:
         occluders, ranges and fields of view)."""
         return self._backend().see(spec, clear, mask, out)
 
+    def frontier_batch(self, seen, spec=None, mask=None, out=None):
+        """The frontier map of EVERY env in one launch, from the memory `seen` of see_batch() on the same grid: Frontier(edge uint8
+        [N, H, W], dist float32 [N, H, W], parent uint8 [N, H, W], count int32 [N], length float32 [N], goal float32 [N, 2], cell int32
+        [N]) on the env's device: where the seen space ends, the field through what is known, and the nearest edge cell as a subgoal
+        (BatchedEnv.frontier; frontier_device.default_spec and spec_like for other grids, sources and optimistic planning)."""
+        return self._backend().frontier(seen, spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

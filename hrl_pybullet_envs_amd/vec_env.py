@@ -141,7 +141,7 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
-    # the sensors (render, scan, probe, field, route, see): each is one launch of a library of its own on the state / items / aux tensors as they are
+    # the sensors (render, scan, probe, field, route, see, frontier): each is one launch of a library of its own on the state / items / aux tensors as they are
     def _default_spec(self, key, make):
         """The spec a sensor uses when none is given: asked of its library once per `key`."""
         specs = self.__dict__.setdefault('_default_specs', {})
@@ -297,6 +297,33 @@ class BatchedEnv:
             raise ValueError(f'clear must be [{self.num_envs}], got {tuple(c.shape)}')
         self._sensor_launch('_last_see_mask', mask, lambda m, stream: V.see(self.cfg, self._bufs_ref, spec, None if c is None else c.data_ptr(), m, out, stream))
         self._last_see_clear = c  # until the stream has consumed it
+        return out
+
+    def frontier(self, seen, spec=None, mask=None, out=None):
+        """The frontier map of every env: a namedtuple Frontier(edge uint8 [N, H, W], dist float32 [N, H, W], parent uint8 [N, H, W], count
+        int32 [N], length float32 [N], goal float32 [N, 2], cell int32 [N]) on this device, from ONE launch on the current stream
+        (frontier_device.py, include/hrl_frontier.h).  `seen`: the memory of see() on the same world grid (uint8 [N, H, W], only read; any
+        non-zero byte counts as seen, and the robot always knows the cell it stands in).  edge = 1 on a known cell that is not blocked and
+        has an unknown orthogonal neighbour inside the grid; dist / parent = the navigation field (field()'s codes) over the known space --
+        an unknown cell is blocked, or free with spec.unknown = OPTIMISTIC -- towards spec.sources: the edge cells (EDGE) and / or the
+        robot, food, poison, the target; count = the number of edge cells (0 = nothing left to explore); length = dist at the robot's
+        cell; goal / cell = the world x, y and row * width + column of the source cell the way from the robot ends on (NaN, -1 and +inf
+        when the robot stands outside the grid, on a blocked cell or cut off).  `spec`: an hrl_frontier_spec
+        (frontier_device.default_spec(cfg, width, height, sources, unknown, margin) or spec_like(cfg, see_spec, ...)); None = the 64 x 64
+        world grid of see(), towards the edge, unknown cells blocked.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh
+        tensors).  `out`: a Frontier of tensors to reuse; a None member is not computed.  The map is of the state / items / aux tensors
+        and of `seen` as they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import frontier_device as X
+        if spec is None:
+            spec = self._default_spec('frontier', lambda: X.default_spec(self.cfg))
+        if not (X.MIN_SIZE <= spec.width <= X.MAX_SIZE and X.MIN_SIZE <= spec.height <= X.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
+            raise ValueError(f'spec.width and spec.height must be within {X.MIN_SIZE}..{X.MAX_SIZE}, got {spec.width} x {spec.height}')
+        X.check_seen(seen, self.num_envs, spec, self.device)
+        if out is None:
+            out = X.Frontier(*(self._fresh(mask, shape, dtype) for shape, (_, dtype) in zip(X.shapes(spec), X.FIELDS)))
+        else:
+            X.check_out(out, self.num_envs, spec, self.device, seen)
+        self._sensor_launch('_last_frontier_mask', mask, lambda m, stream: X.frontier(self.cfg, self._bufs_ref, spec, seen.data_ptr(), m, out, stream))
         return out
 
     def close(self):

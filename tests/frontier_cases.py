@@ -1,0 +1,185 @@
+"""Shared by tests/test_frontier_host.py and tests/test_gpu_frontier.py: the ctypes binding of tests/frontier_host/libfrontier_host.so (the
+host build of csrc/frontier_core.h), the integer numpy logic of include/hrl_frontier.h applied to the host field's own verdicts and to the
+memory, the robot's cell in fp64, and the memories and specs the tests compute maps of.  Test infrastructure only."""
+import collections
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import field_cases as fc
+import see_cases as vc
+from hrl_pybullet_envs_amd import _capi as K
+from hrl_pybullet_envs_amd import field_device as F
+from hrl_pybullet_envs_amd import frontier_device as X
+from hrl_pybullet_envs_amd import see_device as V
+
+ROOT = fc.ROOT
+DIR = os.path.join(ROOT, 'tests', 'frontier_host')
+KINDS = fc.KINDS
+SIZES = fc.SIZES
+GPU_SIZES = fc.GPU_SIZES
+MARGINS = fc.MARGINS
+UNKNOWNS = (X.KNOWN_ONLY, X.OPTIMISTIC)
+SOURCE_BITS = (X.EDGE, X.ROBOT, X.FOOD, X.POISON, X.TARGET)
+SOURCE_SETS = tuple(sum(b for i, b in enumerate(SOURCE_BITS) if m >> i & 1) for m in range(1, 32))   # every admissible source set
+CLASS_SOURCES = X.ROBOT | X.FOOD | X.POISON | X.TARGET
+MEMORIES = ('real', 'ones', 'zeros', 'dirty', 'checkerboard')
+NAMES = tuple(n for n, _ in X.FIELDS)
+DTYPES = (np.uint8, np.float32, np.uint8, np.int32, np.float32, np.float32, np.int32)
+Frontier = collections.namedtuple('Frontier', NAMES)   # of numpy arrays
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        subprocess.check_call(['make', '-s', '-C', DIR, 'libfrontier_host.so'])
+        L = C.CDLL(os.path.join(DIR, 'libfrontier_host.so'))
+        L.frontier_host.argtypes = [C.POINTER(K.hrl_config), C.POINTER(K.hrl_buffers), C.POINTER(X.hrl_frontier_spec), C.c_void_p, C.c_void_p, C.POINTER(X.hrl_frontier_out), C.c_int,
+                                    C.c_void_p]
+        L.frontier_host_last_error.restype = C.c_char_p
+        L.frontier_host_default_spec.argtypes = [C.POINTER(K.hrl_config), C.POINTER(X.hrl_frontier_spec)]
+        L.frontier_sizeof_spec.restype = C.c_ulonglong
+        L.frontier_sizeof_out.restype = C.c_ulonglong
+        L.frontier_validate_spec.argtypes, L.frontier_validate_spec.restype = [C.POINTER(X.hrl_frontier_spec)], C.c_char_p
+        L.frontier_check_case.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_ulonglong)]
+        _lib = L
+    return _lib
+
+
+def check_program():
+    subprocess.check_call(['make', '-s', '-C', DIR, 'frontier_check_main'])
+    return os.path.join(DIR, 'frontier_check_main')
+
+
+ptr = fc.ptr
+
+
+def spec_of(size, margin, sources=X.EDGE, unknown=X.KNOWN_ONLY, blocking=fc.DEFAULT_BLOCKING, half=None, centre=fc.WORLD_CENTRE, kind=None):
+    w, h = size
+    he = half if half is not None else fc.WORLD_HALF[kind]
+    return X.hrl_frontier_spec(width=w, height=h, centre=(C.c_float * 2)(*centre), half_extent=he, blocking=blocking, sources=sources, margin=margin, unknown=unknown)
+
+
+def field_spec(spec, sources):
+    """The field on the map's grid, blocking and margin, towards `sources` (class bits)."""
+    return F.hrl_field_spec(width=spec.width, height=spec.height, mode=F.HRL_VIEW_WORLD, centre=(C.c_float * 2)(*spec.centre), half_extent=spec.half_extent, blocking=spec.blocking,
+                            sources=sources, margin=spec.margin)
+
+
+def see_spec(spec, occluders=V.WALL | V.BOX, fov_cos=-1.0, max_range=vc.HUGE, slack=None):
+    """The visibility map on the map's grid."""
+    return vc.spec_of((spec.width, spec.height), V.HRL_VIEW_WORLD, occluders, fov_cos, max_range, slack, half=spec.half_extent, centre=tuple(spec.centre))
+
+
+def shapes_of(n, spec):
+    h, w = min(max(spec.height, 1), 64), min(max(spec.width, 1), 64)
+    return ((n, h, w), (n, h, w), (n, h, w), (n,), (n,), (n, 2), (n,))
+
+
+def frontier_host(cfg, state, items, aux, spec, seen, mask=None, out=None, want=NAMES, schedule=fc.JACOBI, rounds=None, expect_ok=True):
+    """The host build's map of (state [N, 32] f32, items [N, stride] f32 or None, aux [N, 4] i32, seen [N, H, W] u8): a Frontier of
+    arrays; the members not in `want` are None.  `out`: a Frontier of arrays (None members are passed as NULL) to write into."""
+    state, aux = np.ascontiguousarray(state, np.float32), np.ascontiguousarray(aux, np.int32)
+    items = None if items is None else np.ascontiguousarray(items, np.float32)
+    n = cfg.num_envs
+    assert state.shape == (n, K.HRL_STATE_STRIDE) and aux.shape == (n, K.HRL_AUX_STRIDE)
+    assert seen is None or (seen.dtype == np.uint8 and seen.flags.c_contiguous)
+    if out is None:
+        out = Frontier(*(np.zeros(shape, dt) if name in want else None for name, dt, shape in zip(NAMES, DTYPES, shapes_of(n, spec))))
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    b = K.make_buffers(ptr(state), ptr(items), ptr(aux), None, None, None, None, None)
+    o = X.hrl_frontier_out(**{name: ptr(a) for name, a in zip(NAMES, out)})
+    code = lib().frontier_host(C.byref(cfg), C.byref(b), C.byref(spec), ptr(seen), ptr(m), C.byref(o), schedule, ptr(rounds))
+    if expect_ok:
+        assert code == K.HRL_OK, lib().frontier_host_last_error()
+        return out
+    return code, lib().frontier_host_last_error().decode()
+
+
+def bits(x):
+    return None if x is None else (x.view(np.uint32) if x.dtype == np.float32 else x)
+
+
+def same(a, b):
+    return all((x is None and y is None) or (x is not None and y is not None and np.array_equal(bits(x), bits(y))) for x, y in zip(a, b))
+
+
+# ------------------------------------------------------------------------------------------------ the reference
+def robot_cell(st, spec):
+    """((row, column) or None, gap): the cell of the grid whose square holds the robot of one env, found in fp64 from field_cases.centres,
+    and how close (metres) the robot comes to the edge between two cells of a row or column that could hold it (inf without a robot)."""
+    robot = np.array([st[0], st[1]], float)
+    if not np.isfinite(robot).all() or np.abs(robot).max() > 3.0e38:
+        return None, np.inf
+    _, u, v, (c, right, up) = fc.centres(st, field_spec(spec, F.ROBOT))
+    half = fc.cell_size(spec) / 2
+    du, dv = np.abs(u - (robot - c) @ right), np.abs(v - (robot - c) @ up)
+    gap = float(min(np.abs(du - half).min(), np.abs(dv - half).min()))
+    cols, rows = np.nonzero(du <= half)[0], np.nonzero(dv <= half)[0]
+    return ((int(rows[0]), int(cols[0])) if len(cols) and len(rows) else None), gap
+
+
+def geometry(cfg, state, items, aux, spec):
+    """(blocked, source) [N, H, W] bool from field_host's own verdicts on the map's grid: blocked = the geometry blocks the cell (asked of
+    three fields towards disjoint source sets, since a source cell is free whatever the blocking says; no cell may be a source of all
+    three), source = a source cell of the class part of spec.sources.  g(c) is 0 on source, blocked on blocked & ~source, free otherwise."""
+    pars = [fc.field_host(cfg, state, items, aux, field_spec(spec, s), want=('parent',)).parent for s in (F.ROBOT, F.FOOD, F.POISON | F.TARGET)]
+    assert not np.logical_and.reduce([p == F.SOURCE for p in pars]).any()
+    blocked = np.logical_or.reduce([p == F.BLOCKED for p in pars])
+    cls = spec.sources & CLASS_SOURCES
+    source = fc.field_host(cfg, state, items, aux, field_spec(spec, cls), want=('parent',)).parent == F.SOURCE if cls else np.zeros_like(blocked)
+    return blocked, source
+
+
+def classify(blocked, source, seen, cell, sources, unknown):
+    """include/hrl_frontier.h in integer numpy logic for one env: (edge, blocked cells, source cells) [H, W] bool of the map, from the
+    geometry's verdicts, the memory and the robot's cell (None: it has none)."""
+    known = seen != 0
+    if cell is not None:
+        known[cell] = True
+    g_blocked = blocked & ~source
+    pad = np.ones((known.shape[0] + 2, known.shape[1] + 2), bool)   # beyond the grid: nothing unknown
+    pad[1:-1, 1:-1] = known
+    hidden = ~pad[1:-1, 2:] | ~pad[1:-1, :-2] | ~pad[:-2, 1:-1] | ~pad[2:, 1:-1]
+    edge = known & ~g_blocked & hidden
+    if unknown == X.KNOWN_ONLY:
+        v_blocked, v_source = ~known | g_blocked, known & source
+    else:
+        v_blocked, v_source = known & g_blocked, source.copy()
+    if sources & X.EDGE:
+        v_source |= edge
+        v_blocked &= ~edge
+    return edge, v_blocked, v_source
+
+
+def memory(which, cfg, state, items, aux, spec, seed):
+    """The memory `which` of MEMORIES for every env, uint8 [N, H, W].  'real': the host visibility map (WALL | BOX occlude, a slack of one
+    cell, 4 m of range) accumulated over one to three places of the robot, the last one its own."""
+    n, h, w = cfg.num_envs, spec.height, spec.width
+    rng = np.random.RandomState(seed)
+    if which == 'ones':
+        return np.ones((n, h, w), np.uint8)
+    if which == 'zeros':
+        return np.zeros((n, h, w), np.uint8)
+    if which == 'dirty':
+        return (rng.randint(1, 256, (n, h, w)) * (rng.randint(0, 3, (n, h, w)) == 0)).astype(np.uint8)
+    if which == 'checkerboard':
+        return np.ascontiguousarray(np.broadcast_to(((np.arange(h)[:, None] + np.arange(w)[None, :] + seed) % 2).astype(np.uint8), (n, h, w)))
+    assert which == 'real'
+    out = vc.See(None, np.zeros((n, h, w), np.uint8), None)
+    ss = see_spec(spec, max_range=4.0)
+    for k in range(seed % 3, -1, -1):
+        s = state.copy()
+        if k:
+            s[:, 0:2] += rng.uniform(-3, 3, (n, 2)).astype(np.float32)
+        vc.see_host(cfg, s, items, aux, ss, out=out)
+    return out.seen
+
+
+hand_made = fc.hand_made
+spread = fc.spread
+hostile = fc.hostile
+far_targets = fc.far_targets
