@@ -73,6 +73,20 @@ struct GpuExec {
         asm("v_cndmask_b32_e64 %0, 0, 1.0, %1" : "=v"(d) : "s"(m));
         return d;
     }
+    /* 1.0 on the lanes of a wave-uniform lane mask, 0.0 elsewhere (the same v_cndmask) */
+    __device__ __forceinline__ float lane_in(int, unsigned long long m) {
+        float d;
+        asm("v_cndmask_b32_e64 %0, 0, 1.0, %1" : "=v"(d) : "s"(m));
+        return d;
+    }
+    /* lanes 32 - 63 of `a` and lanes 0 - 31 of `b` change places: v_permlane32_swap_b32 through the builtin, so that the compiler owns the hazard
+     * slots around it (EXPERIMENTS 2: a gfx950 lane read right behind its VALU producer saw the stale register) */
+    template <class A, class B>
+    __device__ __forceinline__ void half_swap(A a, B b) {
+        const auto p = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(a(r)), (unsigned)__float_as_int(b(r)), false, false);
+        a(r) = __int_as_float((int)p[0]);
+        b(r) = __int_as_float((int)p[1]);
+    }
     /* Issue arbitration between the waves of a SIMD goes by priority, then age: with four workgroups per CU at equal priority the
      * first-dispatched one runs at its solo speed and the last one gets the leftover slots, so the launch lasts as long as its
      * slowest workgroup while the mean one is done 13 % earlier (tools/wg_times.py).  slot() = the wave's slot on its SIMD

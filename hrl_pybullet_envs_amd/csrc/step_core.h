@@ -938,14 +938,19 @@ struct LimitHit { bool ok; float sgn, dist; };
 
 /* Phase R1 (row map): Jacobian row and its velocity response B = M^-1 J^T.  J, bias and bounds stay in the lane's
  * registers, B goes to LDS (every row needs every B to build its row of A).  Contacts between two ant bodies get the
- * first body's part here and the second body's in phase_self_rows. */
-HRL_DEV void phase_build_row(const DevCfg &c, WaveLds &L, LaneRegs &g, int lane, int nL, int nC) {
+ * first body's part here and the second body's in phase_self_rows.
+ * `mirror` (wave-uniform: the substep builds its lines of C on both half-waves, halfwave_rows): lane 32 + i holds the
+ * Jacobian of row i as well -- same loads, same operations, so bit for bit lane i's -- and builds row i's friction columns
+ * in phase R2 while lane i builds the bounded ones.  A mirror lane is no row: it stores no B, keeps fn = -1, and what it
+ * leaves in lam / lo / hi / c is defined but read by no row lane. */
+HRL_DEV void phase_build_row(const DevCfg &c, WaveLds &L, LaneRegs &g, int lane, int nL, int nC, bool mirror = false) {
     const int nR = nL + 3 * nC;
-    /* Lanes beyond the last row recompute row 0 and discard it: every lane then (re)defines all of its solver
-     * registers each substep, so none of them stays live around the substep loop (a partially written register
+    /* Lanes beyond the last row (and its mirror) recompute row 0 and discard it: every lane then (re)defines all of its
+     * solver registers each substep, so none of them stays live around the substep loop (a partially written register
      * would, and the 60 of them would be spilled in the register-hungry leg phases). */
     const bool active = lane < nR;
-    const int row_id = active ? lane : 0;
+    const int own = mirror ? (lane & 31) : lane;
+    const int row_id = own < nR ? own : 0;
     float B[16], bias, hi = 0.f, Jh = 0.f, Ja = 0.f, mu = 0.f;
     int frn = -1;
     if (nR == 0) { /* no rows this substep (wave-uniform): still define every register */
@@ -1126,6 +1131,91 @@ HRL_DEV void build_A_blocks(const WaveLds &L, LaneRegs &g, int nB, int nF, float
     (build_An_group<SELF, Gn, WIDE>(L, g, nB, ninvd, one, j2), ...);
     (build_Af_group<SELF, Gf, WIDE>(L, g, nB, nF, ninvd, one, j2), ...);
 }
+/* R2 ON BOTH HALF-WAVES (the ant kinds; substeps with at most 32 rows and no self contact, halfwave_rows): lane 32 + i mirrors row i
+ * (phase_build_row), so one pass of row_dot4 over all 64 lanes builds four BOUNDED columns of every row on the lower half-wave and four
+ * FRICTION columns of every row on the upper one -- max(nB, nF) / 4 passes where build_A_blocks runs nB / 4 + nF / 4 groups one after the
+ * other, each with its own LDS round trip.  The two halves differ in the base of their B rows, chosen once (`Bh`: Bt + 0 | nB; the four row
+ * addresses of a pass are that base plus compile-time offsets), and in the lane of their unit diagonal (`one`: row 4G + i's is lane
+ * 4G + i below, lane 32 + nB + 4G + i above).  Every lane leaves its four values in An[4G .. 4G + 3] and zeros in Af; halfwave_rows_home
+ * then exchanges the upper half of An[4G + i] with the lower half of Af[4G + i].  Per value the operations and operands are build_An_group's / build_Af_group's.
+ * A half whose block ends before the other's computes from whatever LDS holds (base + 4G + 3 <= nB + max(nB, nF) + 2 <= 34 with at most
+ * 32 rows: inside Bt); so do lanes that are no row or mirror of one.  The sweeps read An[R] only for R < nB and Af[K] only for K < nF
+ * (pgs_row_bounded, pgs_row_friction), and only what the lanes < nR make of them is kept (lam of lanes < nR), so no such value reaches a
+ * result.  With at most 32 rows there are at most 10 contacts: nF <= 20 and five passes reach every column; Af[20 .. 23] are zeroed. */
+constexpr int HALF_PASSES = 5;
+static_assert(4 * HALF_PASSES >= MAXB && 4 * HALF_PASSES >= 2 * (32 / 3) && 4 * HALF_PASSES <= MAXF, "five passes cover the bounded and the friction columns of 32 rows");
+HRL_DEV bool halfwave_rows(int nR, bool self) { return (nR <= 32) & !self; } /* wave-uniform */
+template <int G, class OneH>
+HRL_DEV void build_half_group(const float (*Bh)[16], LaneRegs &g, int mx, float ninvd, OneH one, const J2pair &j2) {
+    if (4 * G < mx) {
+        float a[4];
+        row_dot4<false>(g, Bh[4 * G], Bh[4 * G + 1], Bh[4 * G + 2], Bh[4 * G + 3], j2, a);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g.An[4 * G + i] = fma_(ninvd, a[i], one(4 * G + i));
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g.An[4 * G + i] = 0.f;
+    }
+}
+template <class OneH, int... Gs>
+HRL_DEV void build_half_passes(const float (*Bh)[16], LaneRegs &g, int mx, float ninvd, OneH one, const J2pair &j2, std::integer_sequence<int, Gs...>) {
+    (build_half_group<Gs>(Bh, g, mx, ninvd, one, j2), ...);
+    /* Af is defined HERE on every path, not by the exchange alone: that sits behind a test of its own, and a register written on some paths
+     * only stays live around the substep loop and is spilled (phase_build_row).  The zeros are also what the exchange hands the upper half. */
+#pragma unroll
+    for (int k = 0; k < MAXF; ++k) g.Af[k] = 0.f;
+}
+/* one(k): the unit diagonal of column k of BOTH halves, supplied by the executor (1 on lane k and on lane 32 + nB + k) */
+template <class OneH>
+HRL_DEV void phase_build_A_halves(const DevCfg &c, const WaveLds &L, LaneRegs &g, int lane, int nL, int nB, int nF, OneH one) {
+    const J2pair j2{0.f, 0.f};
+    const int nR = nB + nF, own = lane & 31, row = own < nR ? own : 0; /* the lane's row, or the row it mirrors; idle lanes carry row 0's registers */
+    if (c.restitution > 0.f) { /* as in phase_build_A; a mirror lane is no normal row and keeps its bias */
+        const float vn = row_dot<false>(g, L.u, j2);
+        const bool normal = (lane >= nL) & (lane < nB);
+        g.bias = (normal & (vn < -c.rest_thr)) ? fma_(c.restitution, vn, g.bias) : g.bias;
+    }
+    const float invd = 1.f / row_dot<false>(g, L.Bt[row], j2); /* 1 / A_ii of the row on both of its lanes */
+    const float (*Bh)[16] = L.Bt + (lane >= 32 ? nB : 0);
+    build_half_passes(Bh, g, nB > nF ? nB : nF, -invd, one, j2, std::make_integer_sequence<int, HALF_PASSES>{});
+    g.c = -(invd * (row_dot<false>(g, L.ustar, j2) + g.bias));
+}
+/* The two executor primitives of the build on both half-waves.  On the device they are the executor's own (GpuExec::half_swap, one
+ * v_permlane32_swap_b32; GpuExec::lane_in, one v_cndmask on a scalar lane mask).  A lock-step host executor holds every lane's registers
+ * (x.reg(l) is lane l's), so for it they are written out here, in terms of what every executor already has:
+ *   half_swap(x, a, b): lanes 32 - 63 of register a and lanes 0 - 31 of register b change places (an exchange: no lane order to it);
+ *   lane_in(x, lane, m): 1.0 on the lanes of the wave-uniform lane mask m, 0.0 elsewhere. */
+template <class X, class A, class B>
+HRL_DEV void half_swap(X &x, A a, B b) {
+#ifdef HRL_EMU
+    for (int l = 0; l < 32; ++l) { const float t = a(x.reg(l + 32)); a(x.reg(l + 32)) = b(x.reg(l)); b(x.reg(l)) = t; }
+#else
+    x.half_swap(a, b);
+#endif
+}
+template <class X>
+HRL_DEV float lane_in(X &x, int lane, unsigned long long m) {
+#ifdef HRL_EMU
+    (void)x;
+    return (m >> lane) & 1ull ? 1.f : 0.f;
+#else
+    return x.lane_in(lane, m);
+#endif
+}
+/* the friction columns come home: lanes 0 - 31 of Af[4G + i] receive what lanes 32 - 63 left in An[4G + i] (half_swap; those lanes of An
+ * take the zeros of Af in exchange), behind the test of the pass that built them; the groups beyond it stay zero */
+template <int G, class X>
+HRL_DEV void halfwave_group_home(X &x, int mx) {
+    if (4 * G < mx) {
+        half_swap(x, [](LaneRegs &g) -> float & { return g.An[4 * G]; }, [](LaneRegs &g) -> float & { return g.Af[4 * G]; });
+        half_swap(x, [](LaneRegs &g) -> float & { return g.An[4 * G + 1]; }, [](LaneRegs &g) -> float & { return g.Af[4 * G + 1]; });
+        half_swap(x, [](LaneRegs &g) -> float & { return g.An[4 * G + 2]; }, [](LaneRegs &g) -> float & { return g.Af[4 * G + 2]; });
+        half_swap(x, [](LaneRegs &g) -> float & { return g.An[4 * G + 3]; }, [](LaneRegs &g) -> float & { return g.Af[4 * G + 3]; });
+    }
+}
+template <class X, int... Gs>
+HRL_DEV void halfwave_rows_home(X &x, int mx, std::integer_sequence<int, Gs...>) { (halfwave_group_home<Gs>(x, mx), ...); }
+
 template <bool SELF, int MB, class One> /* MB = most bounded rows the caller can have (a multiple of four): columns past it are not built */
 HRL_DEV void phase_build_A(const DevCfg &c, const WaveLds &L, LaneRegs &g, int lane, int nL, int nB, int nF, One one) {
     J2pair j2{0.f, 0.f};
@@ -1238,7 +1328,13 @@ HRL_DEV void pgs_solve(X &x, const DevCfg &c, int nL, int nC, bool ant, bool sel
     const int nB = ant ? nL + nC : nC, nF = 2 * nC, nR = nB + nF;
     if (nR <= 0) return;
     const int nLim = ant ? nL : 0;
-    if (self) x.each([&](int lane) { phase_build_A<true, MB>(c, L, x.reg(lane), lane, nLim, nB, nF, [&](int r) { return x.lane_one(lane, r); }); });
+    bool halves = false;
+    if constexpr (MB == MAXB) halves = ant && halfwave_rows(nR, self); /* wave-uniform; every other substep, and the point bot, build as before */
+    if (halves) {
+        const unsigned long long diag = 1ull | (1ull << (32 + nB)); /* nB <= MAXB: the shift stays below 64; columns whose upper lane would be past 63 drop out of the mask */
+        x.each([&](int lane) { phase_build_A_halves(c, L, x.reg(lane), lane, nLim, nB, nF, [&](int k) { return lane_in(x, lane, diag << k); }); });
+        halfwave_rows_home(x, nB > nF ? nB : nF, std::make_integer_sequence<int, HALF_PASSES>{});
+    } else if (self) x.each([&](int lane) { phase_build_A<true, MB>(c, L, x.reg(lane), lane, nLim, nB, nF, [&](int r) { return x.lane_one(lane, r); }); });
     else x.each([&](int lane) { phase_build_A<false, MB>(c, L, x.reg(lane), lane, nLim, nB, nF, [&](int r) { return x.lane_one(lane, r); }); });
     if (MB != MAXB) /* the point bot's kernel sits at its register cap: lines spilled around the build are reloaded HERE, not inside the sweeps */
         x.each([&](int lane) {
@@ -1530,7 +1626,7 @@ HRL_DEV int ant_env_block(X &x, const DevCfg &c, int qi) { /* returns the subste
 #endif
     x.each([&](int lane) {
         x.reg(lane).ud = L.ustar[lane & 15]; /* the velocity if no row turns up */
-        phase_build_row(c, L, x.reg(lane), lane, nL, nC);
+        phase_build_row(c, L, x.reg(lane), lane, nL, nC, halfwave_rows(nL + 3 * nC, nS > 0));
     });
     if (nS > 0) x.each([&](int lane) { phase_self_rows(c, L, x.reg(lane), lane, nL, nC); });
     x.stamp(7);
