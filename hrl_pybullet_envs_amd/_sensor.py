@@ -1,4 +1,4 @@
-"""What the bindings of the sensor libraries share (render_device.py, scan_device.py, probe_device.py, field_device.py, route_device.py, see_device.py): the base of their
+"""What the bindings of the sensor libraries share (render_device.py, scan_device.py, probe_device.py, field_device.py, route_device.py, see_device.py, frontier_device.py, camera_device.py): the base of their
 spec records, the loader of a library, the check of the tensors handed in as `out=`, and the record of output pointers."""
 import ctypes as C
 import os

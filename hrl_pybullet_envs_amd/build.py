@@ -3,8 +3,8 @@ hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_re
 (the batched range scanner, include/hrl_scan.h), hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
 include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h),
 hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h), hrl_pybullet_envs_amd/libhrl_see_hip.so (the
-batched visibility map, include/hrl_see.h) and hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map,
-include/hrl_frontier.h).
+batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map, include/hrl_frontier.h) and
+hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -29,6 +29,8 @@ ROUTE = ('route', 'libhrl_route_hip.so', 'route_hip.hip', 'route_core.h', 'hrl_r
 SEE = ('see', 'libhrl_see_hip.so', 'see_hip.hip', 'see_core.h', 'hrl_see.h')
 # The frontier map stands on the field's chain and on the routes' specification (the test that names a point's cell, the cell-to-world function).
 FRONTIER = ('frontier', 'libhrl_frontier_hip.so', 'frontier_hip.hip', 'frontier_core.h', 'hrl_frontier.h')
+# The first-person camera stands on the scanner's chain alone (render, scan): the scanner's table plus a z-interval per slot.
+CAMERA = ('camera', 'libhrl_camera_hip.so', 'camera_hip.hip', 'camera_core.h', 'hrl_camera.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -113,8 +115,18 @@ def build_frontier(force=False, verbose=False):
     return _build_on_the_field(FRONTIER, force, verbose, (ROUTE[3],), (ROUTE[4],))
 
 
+def build_camera(force=False, verbose=False):
+    """The first-person camera's library; returns its path.  It depends on everything the scanner depends on plus its own three files."""
+    _, lib, source, core, header = CAMERA
+    lib = os.path.join(PKG, lib)
+    sources = [source, core, 'sensor_launch.h'] + [c for *_, c, _ in SENSORS[:2]] + SOURCES[1:]
+    if force or _stale(lib, sources, ['hrl_envs.h', header] + [h for *_, h in SENSORS[:2]]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The eight libraries; returns the step library's path."""
+    """The nine libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
@@ -122,10 +134,11 @@ def build(force=False, verbose=False):
     build_route(force, verbose)
     build_see(force, verbose)
     build_frontier(force, verbose)
+    build_camera(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA]:
         print(os.path.join(PKG, lib))

@@ -237,6 +237,12 @@ class BatchedGymEnv:
         (BatchedEnv.frontier; frontier_device.default_spec and spec_like for other grids, sources and optimistic planning)."""
         return self._backend().frontier(seen, spec, mask, out)
 
+    def camera_batch(self, spec=None, mask=None, out=None):
+        """The first-person image of EVERY env in one launch: Camera(depth float32 [N, H, W], seg int32 [N, H, W], rgb uint8 [N, H, W, 3])
+        on the env's device: what a pinhole camera over each robot sees of the walls, the maze box, the items, the target and the ground
+        (BatchedEnv.camera; camera_device.default_spec for other sizes, fields of view, eye heights and classes)."""
+        return self._backend().camera(spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

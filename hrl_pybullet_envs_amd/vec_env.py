@@ -141,7 +141,7 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
-    # the sensors (render, scan, probe, field, route, see, frontier): each is one launch of a library of its own on the state / items / aux tensors as they are
+    # the sensors (render, scan, probe, field, route, see, frontier, camera): each is one launch of a library of its own on the state / items / aux tensors as they are
     def _default_spec(self, key, make):
         """The spec a sensor uses when none is given: asked of its library once per `key`."""
         specs = self.__dict__.setdefault('_default_specs', {})
@@ -324,6 +324,28 @@ class BatchedEnv:
         else:
             X.check_out(out, self.num_envs, spec, self.device, seen)
         self._sensor_launch('_last_frontier_mask', mask, lambda m, stream: X.frontier(self.cfg, self._bufs_ref, spec, seen.data_ptr(), m, out, stream))
+        return out
+
+    def camera(self, spec=None, mask=None, out=None):
+        """The first-person image of every env: a namedtuple Camera(depth float32 [N, H, W], seg int32 [N, H, W], rgb uint8 [N, H, W, 3]) on
+        this device, from ONE launch on the current stream (camera_device.py, include/hrl_camera.h).  A pinhole camera over the robot that
+        yaws with spec.frame and neither pitches nor rolls sees the walls, the maze box, the item cubes, the target post and the ground as
+        solids: depth = metres along the optical axis (spec.max_range where nothing was hit), seg = the scanner's hit code | face << 16
+        (camera_device.decode), rgb = the class colour shaded by face, the sky where nothing was hit.  `spec`: an hrl_camera_spec
+        (camera_device.default_spec(cfg, frame, width, height, hfov_degrees, vfov_degrees, eye, eye_height, max_range, classes)); None =
+        64 x 48 pixels, 90 degrees, from the torso, turning with the heading.  Envs with mask[i] == 0 keep what `out` holds (zeros in
+        fresh tensors).  `out`: a Camera of tensors to reuse; a None member is not computed.  The image is of the state / items / aux
+        tensors as they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import camera_device as Cm
+        if spec is None:
+            spec = self._default_spec('camera', lambda: Cm.default_spec(self.cfg))
+        if out is None:
+            if not Cm.sized(spec):   # (the library refuses it too; no tensor can be shaped after it)
+                raise ValueError(f'spec.width must be within {Cm.MIN_WIDTH}..{Cm.MAX_SIZE} and spec.height within {Cm.MIN_HEIGHT}..{Cm.MAX_SIZE}, got {spec.width} x {spec.height}')
+            out = Cm.Camera(*(self._fresh(mask, shape, dtype) for shape, (_, dtype) in zip(Cm.shapes(spec), Cm.FIELDS)))
+        else:
+            Cm.check_out(out, self.num_envs, spec, self.device)
+        self._sensor_launch('_last_camera_mask', mask, lambda m, stream: Cm.camera(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
     def close(self):

@@ -1,0 +1,138 @@
+"""The guards of the first-person camera's library (libhrl_camera_hip.so) that return before a device is looked for, and what its Python
+binding refuses before it calls, in the form of test_sensor_launch.py.  CPU only: every call below returns before the HIP runtime is asked
+anything, so the results are the same with and without a GPU.  The phrases are copied from csrc/camera_hip.hip and csrc/camera_core.h."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from hrl_pybullet_envs_amd import _capi as K
+from hrl_pybullet_envs_amd import _lib
+from hrl_pybullet_envs_amd import camera_device as Cm
+from test_sensor_launch import BASE, N, STRUCT_SIZE, unaligned
+from test_sensor_launch import Call as Other
+
+OUTPUTS = tuple(n for n, _ in Cm.FIELDS)
+
+
+class Call:
+    """One launch on 2 envs of the flat kind with host memory behind every pointer (none is read: the calls are refused first).  `addr`:
+    the address of each output, to be moved or nulled by a test."""
+
+    def __init__(self, frame='heading'):
+        self.cfg = _lib.default_config(K.HRL_ANT_FLAT, num_envs=N)
+        self.spec = Cm.default_spec(self.cfg, frame)
+        self.keep = [np.zeros(N * K.HRL_STATE_STRIDE, np.float32), np.zeros(N * K.HRL_AUX_STRIDE, np.int32)]
+        self.bufs = K.make_buffers(self.keep[0].ctypes.data, None, self.keep[1].ctypes.data, None, None, None, None, None)
+        self.addr = {o: self.room(N * 48 * 64 * 4) for o in OUTPUTS}
+
+    def room(self, nbytes):
+        a = np.full(nbytes + 128, 0x7B, np.uint8)
+        self.keep.append(a)
+        return (a.ctypes.data + 63) // 64 * 64
+
+    def __call__(self, record=True, out=True):
+        o = Cm.hrl_camera_out(**self.addr)
+        return Cm.lib().hrl_camera(C.byref(self.cfg), C.byref(self.bufs) if record else None, C.byref(self.spec), None, C.byref(o) if out else None, None)
+
+    def last_error(self):
+        return Cm.lib().hrl_camera_last_error().decode()
+
+    def refused(self, phrase, **kw):
+        assert self(**kw) == K.HRL_ERR_BAD_ARG
+        why = self.last_error()
+        assert why.startswith('hrl_camera: ') and phrase in why, why
+        assert all((a == 0x7B).all() for a in self.keep[2:])   # nothing was written
+
+
+def test_buffer_record_guards():
+    c = Call()
+    c.refused('null buffer record', record=False)
+    for size in (0, BASE - 8, 4104, BASE + 4):
+        c.bufs.struct_size = size
+        c.refused(STRUCT_SIZE)
+    for member in ('state', 'aux'):
+        c = Call()
+        setattr(c.bufs, member, None)
+        c.refused('null state or aux')
+
+
+def test_output_guards():
+    for output in OUTPUTS:
+        c = Call()
+        for _ in range(3):   # 1, 2 and 3 bytes past a multiple of 4
+            c.addr[output] += 1
+            c.refused(f'{output} must be 4-byte aligned')
+    c = Call()
+    for output in OUTPUTS:
+        c.addr[output] = None
+    c.refused('camera out holds no pointer: at least one output must be given')
+    Call().refused('null camera out', out=False)
+
+
+def test_config_and_spec_guards_come_first():
+    """A config hrl_create() would refuse and a bad spec are named before the buffer record is looked at."""
+    c = Call()
+    c.cfg.num_envs = 0
+    assert c(record=False) == K.HRL_ERR_BAD_ARG and c.last_error().startswith('hrl_camera: ') and 'null buffer record' not in c.last_error()
+    for field, value, phrase in (('width', 24, 'camera width must be a multiple of 16 within 16..128'), ('height', 132, 'camera height must be a multiple of 8 within 8..128'),
+                                 ('frame', 2, 'unknown camera frame'), ('eye_mode', 2, 'unknown camera eye_mode'), ('eye_height', 11.0, 'camera eye_height must be finite and within 0..10'),
+                                 ('tan_half_h', 0.0, 'camera tan_half_h must be finite'), ('tan_half_v', float('nan'), 'camera tan_half_v must be finite'),
+                                 ('max_range', float('inf'), 'camera max_range must be finite and positive'), ('classes', 0, 'camera classes must be a non-empty mask'),
+                                 ('classes', 32, 'camera classes must be a non-empty mask'), ('struct_size', 40, 'hrl_camera_spec.struct_size is not sizeof(hrl_camera_spec)')):
+        c = Call()
+        setattr(c.spec, field, value)
+        c.refused(phrase, record=False)
+    s = Cm.hrl_camera_spec()
+    assert Cm.lib().hrl_camera_default_spec(None, 0, C.byref(s)) == K.HRL_ERR_BAD_ARG and Cm.lib().hrl_camera_last_error().startswith(b'hrl_camera_default_spec: ')
+    assert Cm.lib().hrl_camera_default_spec(C.byref(Call().cfg), 2, C.byref(s)) == K.HRL_ERR_BAD_ARG
+
+
+def test_a_refusal_stays_in_its_own_library():
+    """The libraries live in one process; each keeps its own error string."""
+    mine, scan = Call(), Other('scan')
+    scan.refused('null buffer record', record=False)
+    before = scan.last_error()
+    mine.spec.classes = 0
+    mine.refused('camera classes must be a non-empty mask')
+    assert scan.last_error() == before and before.startswith('hrl_scan: ')
+    why = mine.last_error()
+    scan.bufs.struct_size = 0
+    scan.refused(STRUCT_SIZE)
+    assert mine.last_error() == why
+
+
+def test_check_out_on_host_tensors():
+    """What BatchedEnv.camera hands to the binding's check, with host tensors against an env on cuda:0: the exception types that the GPU
+    test `test_out_is_reused_and_checked` expects, and their texts."""
+    dev, cpu = torch.device('cuda:0'), torch.device('cpu')
+    cfg = _lib.default_config(K.HRL_ANT_FLAT, num_envs=N)
+    spec = Cm.default_spec(cfg, 'world', 48, 24)
+    out = Cm.Camera(torch.zeros(N, 24, 48), torch.zeros(N, 24, 48, dtype=torch.int32), torch.zeros(N, 24, 48, 3, dtype=torch.uint8))
+    assert Cm.check_out(out, N, spec, cpu) is out
+    assert Cm.check_out(Cm.Camera(seg=out.seg), N, spec, cpu).seg is out.seg   # None members are skipped
+    with pytest.raises(TypeError, match='out must be a camera_device.Camera'):
+        Cm.check_out(tuple(out), N, spec, dev)
+    with pytest.raises(TypeError, match='out.depth must be a torch.float32 tensor'):
+        Cm.check_out(out._replace(depth=out.depth.double()), N, spec, dev)
+    with pytest.raises(TypeError, match='out.seg must be a torch.int32 tensor'):
+        Cm.check_out(out._replace(seg=out.seg.long()), N, spec, cpu)
+    with pytest.raises(TypeError, match='out.rgb must be a torch.uint8 tensor'):
+        Cm.check_out(out._replace(rgb=out.rgb.float()), N, spec, cpu)
+    with pytest.raises(ValueError, match=r'out.depth must be contiguous \(2, 24, 48\)'):
+        Cm.check_out(out._replace(depth=torch.zeros(N, 48, 24)), N, spec, dev)
+    with pytest.raises(ValueError, match=r'out.rgb must be contiguous \(2, 24, 48, 3\)'):
+        Cm.check_out(out._replace(rgb=torch.zeros(N, 24, 48, 4, dtype=torch.uint8)[..., :3]), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.seg must be contiguous'):
+        Cm.check_out(out._replace(seg=torch.zeros(N, 24, 96, dtype=torch.int32)[..., ::2]), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.depth lives on cpu, the env on cuda:0'):
+        Cm.check_out(out, N, spec, dev)
+    with pytest.raises(ValueError, match='out holds no tensor'):
+        Cm.check_out(Cm.Camera(), N, spec, dev)
+    with pytest.raises(ValueError, match='out.rgb must be 4-byte aligned'):
+        Cm.check_out(out._replace(rgb=unaligned((N, 24, 48, 3), torch.uint8, 2)), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.depth and out.seg must not be the same memory'):
+        Cm.check_out(out._replace(seg=out.depth.view(torch.int32)), N, spec, cpu)
+    assert Cm.sized(spec) and not Cm.sized(Cm.hrl_camera_spec(width=256, height=24)) and not Cm.sized(Cm.hrl_camera_spec(width=48, height=0))
+
