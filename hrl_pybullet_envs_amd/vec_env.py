@@ -112,6 +112,7 @@ class BatchedEnv:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().hrl_update_config(self._h, C.byref(cfg), self._stream()))
         self.cfg = cfg
+        self.__dict__.pop('_default_specs', None)   # the sensors' default specs are derived from the config (the arena's extent): asked again
 
     def count_solver_rows(self, on=True):
         """Diagnostic: from now on every step ADDS to `self.solver_rows` [N] (int32, zeroed here) the constraint rows each env's solver held

@@ -62,7 +62,7 @@ ptr = rc.ptr
 
 def spec_of(size, mode, margin, sources, blocking=DEFAULT_BLOCKING, half=None, centre=(0.0, 0.0), kind=None):
     w, h = size
-    he = half if half is not None else (WORLD_HALF[kind] if mode == F.HRL_VIEW_WORLD else EGO_HALF)
+    he = half if half is not None else (rc.world_half(kind) if mode == F.HRL_VIEW_WORLD else EGO_HALF)   # kind: an env kind or a config
     return F.hrl_field_spec(width=w, height=h, mode=mode, centre=(C.c_float * 2)(*centre), half_extent=he, blocking=blocking, sources=sources, margin=margin)
 
 

@@ -59,7 +59,7 @@ ptr = fc.ptr
 
 def spec_of(size, margin, sources=X.EDGE, unknown=X.KNOWN_ONLY, blocking=fc.DEFAULT_BLOCKING, half=None, centre=fc.WORLD_CENTRE, kind=None):
     w, h = size
-    he = half if half is not None else fc.WORLD_HALF[kind]
+    he = half if half is not None else fc.rc.world_half(kind)   # kind: an env kind or a config
     return X.hrl_frontier_spec(width=w, height=h, centre=(C.c_float * 2)(*centre), half_extent=he, blocking=blocking, sources=sources, margin=margin, unknown=unknown)
 
 

@@ -307,6 +307,9 @@ def spread(cfg, state):
     side, in the far corner behind it, a metre from two walls, and below the box (the shards' robots all stand near the start)."""
     s = state.copy()
     s[:5, 0:2] = SPREAD
+    ar = arena(cfg)
+    if ar is not None and ar != rc.DEFAULT_ARENA[cfg.env_kind]:   # another arena than the kind's default: the same places, scaled from the maze's 5 x 9 into it
+        s[:5, 0:2] = np.array(SPREAD) * (ar[0] / 5.0, ar[1] / 9.0)
     return s
 
 

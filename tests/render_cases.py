@@ -44,9 +44,21 @@ def ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def world_half(kind):
+    """The half extent of the world views and grids of the tests: WORLD_HALF of a kind; of a config (tests/sensor_configs.py) its kind's
+    too where the arena is the kind's default one (or there is none), else the arena's longer half side + 0.2 m."""
+    if isinstance(kind, int):
+        return WORLD_HALF[kind]
+    ar = arena(kind)
+    if ar is None or ar == DEFAULT_ARENA[kind.env_kind]:
+        return WORLD_HALF[kind.env_kind]
+    return round(max(ar) + 0.05 + 0.2, 3)
+
+
 def view_of(kind, mode, size, half=None):
+    """`kind`: an env kind, or a config whose arena need not be the kind's default one (world_half)."""
     w, h = size
-    he = half if half is not None else (WORLD_HALF[kind] if mode == R.HRL_VIEW_WORLD else EGO_HALF)
+    he = half if half is not None else (world_half(kind) if mode == R.HRL_VIEW_WORLD else EGO_HALF)
     return R.hrl_view(width=w, height=h, mode=mode, centre=(C.c_float * 2)(0.0, 0.0), half_extent=he)
 
 
@@ -120,6 +132,10 @@ def arena(cfg):
     if k in (K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ):
         return 5 - 0.05, 9 - 0.05
     return None
+
+
+DEFAULT_ARENA = {K.HRL_ANT_FLAT: None, K.HRL_ANT_GATHER: (15 / 2 - 0.05, 15 / 2 - 0.05), K.HRL_POINT_GATHER: (15 / 2 - 0.05, 15 / 2 - 0.05), K.HRL_ANT_MAZE: (5 - 0.05, 9 - 0.05),
+                 K.HRL_ANT_MAZE_MJ: (5 - 0.05, 9 - 0.05), K.HRL_ANT_FLAGRUN: (12 / 2 - 0.05, 12 / 2 - 0.05)}   # arena() of the default config of each kind
 
 
 def shapes(cfg, st, items, aux):

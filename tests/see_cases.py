@@ -55,7 +55,7 @@ ptr = rc.ptr
 def spec_of(size, mode, occluders=V.WALL | V.BOX, fov_cos=-1.0, max_range=HUGE, slack=0.0, half=None, centre=(0.0, 0.0), kind=None):
     """slack = None: one cell of the grid (see_device.one_cell: at most the 2 m the header allows)."""
     w, h = size
-    he = half if half is not None else (fc.WORLD_HALF[kind] if mode == V.HRL_VIEW_WORLD else fc.EGO_HALF)
+    he = half if half is not None else (rc.world_half(kind) if mode == V.HRL_VIEW_WORLD else fc.EGO_HALF)   # kind: an env kind or a config
     s = V.hrl_see_spec(width=w, height=h, mode=mode, centre=(C.c_float * 2)(*centre), half_extent=he, occluders=occluders, max_range=max_range, fov_cos=fov_cos, slack=0.0)
     s.slack = V.one_cell(s) if slack is None else slack
     return s

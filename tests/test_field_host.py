@@ -15,6 +15,7 @@ import pytest
 import field_cases as fc
 import orc
 import probe_cases as pc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import field_device as F
 from hrl_pybullet_envs_amd import probe_device as P
@@ -48,30 +49,60 @@ def test_host_build_equals_the_fp64_reference(kind):
     over this sweep: 1.53e-5 m (the maze kinds; 4.9e-6 .. 8.2e-6 m elsewhere); asserted at 4 x that, 6.1e-5 m.  Most Jacobi rounds: 89
     (maze), 60 .. 65 elsewhere."""
     cfg, state, items, aux = shard(kind)
-    worst, turn, exempt_worst, rounds_worst = 0.0, 0, 0.0, 0
-    for mode in fc.MODES:
-        for size in fc.SIZES:
-            for margin in fc.MARGINS:
-                for label, st in states_of(cfg, state):
-                    sources = fc.SOURCE_SETS[turn % len(fc.SOURCE_SETS)]
-                    turn += 1
-                    spec = fc.spec_of(size, mode, margin, sources, kind=kind, centre=fc.WORLD_CENTRE)
-                    where = (kind, mode, size, margin, label, sources)
-                    refs = [fc.geometry(cfg, st[e], None if items is None else items[e], aux[e], spec) for e in range(N)]
-                    exempt = sum(r[2].sum() for r in refs) / (N * size[0] * size[1])   # on the reference alone, before the build is looked at
-                    assert exempt <= 0.01, (where, exempt)
-                    exempt_worst = max(exempt_worst, exempt)
-                    rounds = np.zeros(N, np.int32)
-                    got = fc.field_host(cfg, st, items, aux, spec, rounds=rounds)
-                    rounds_worst = max(rounds_worst, int(rounds.max()))
-                    for e, (blocked, source, near) in enumerate(refs):
-                        par = got.parent[e]
-                        bad = ((par == F.BLOCKED) != blocked) & ~near
-                        assert not bad.any(), (where, e, 'blocked', np.argwhere(bad)[:4])
-                        bad = ((par == F.SOURCE) != source) & ~near
-                        assert not bad.any(), (where, e, 'source', np.argwhere(bad)[:4])
-                        worst = max(worst, fc.check_propagation(fc.Field(got.dist[e], par), spec, TOL))
+    specs = [(fc.spec_of(size, mode, margin, F.ROBOT, kind=kind, centre=fc.WORLD_CENTRE), None) for mode in fc.MODES for size in fc.SIZES for margin in fc.MARGINS]
+    worst, exempt_worst, rounds_worst = compare_with_the_reference(cfg, state, items, aux, specs, kind)
     print(f'kind {kind}: worst |dist - reference| {worst:.3g} m, most exempt cells {100 * exempt_worst:.2f} %, most Jacobi rounds {rounds_worst}')
+
+
+def compare_with_the_reference(cfg, state, items, aux, specs, tag):
+    """The comparison of test_host_build_equals_the_fp64_reference on the given states, their hand-made poses and with the robots spread
+    about the arena.  `specs`: pairs (spec, sources); sources None = the admissible source sets taken in turn.  Returns (the worst
+    |dist - reference| in metres, the largest share of exempt cells of a case, the most Jacobi rounds)."""
+    worst, turn, exempt_worst, rounds_worst = 0.0, 0, 0.0, 0
+    for base, fixed in specs:
+        for label, st in states_of(cfg, state):
+            spec = base.copy()
+            spec.sources = fixed if fixed is not None else fc.SOURCE_SETS[turn % len(fc.SOURCE_SETS)]
+            turn += 1
+            where = (tag, spec.mode, (spec.width, spec.height), spec.margin, label, spec.sources)
+            refs = [fc.geometry(cfg, st[e], None if items is None else items[e], aux[e], spec) for e in range(N)]
+            exempt = sum(r[2].sum() for r in refs) / (N * spec.width * spec.height)   # on the reference alone, before the build is looked at
+            assert exempt <= 0.01, (where, exempt)
+            exempt_worst = max(exempt_worst, exempt)
+            rounds = np.zeros(N, np.int32)
+            got = fc.field_host(cfg, st, items, aux, spec, rounds=rounds)
+            rounds_worst = max(rounds_worst, int(rounds.max()))
+            for e, (blocked, source, near) in enumerate(refs):
+                par = got.parent[e]
+                bad = ((par == F.BLOCKED) != blocked) & ~near
+                assert not bad.any(), (where, e, 'blocked', np.argwhere(bad)[:4])
+                bad = ((par == F.SOURCE) != source) & ~near
+                assert not bad.any(), (where, e, 'source', np.argwhere(bad)[:4])
+                worst = max(worst, fc.check_propagation(fc.Field(got.dist[e], par), spec, TOL))
+    return worst, exempt_worst, rounds_worst
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_host_build_equals_the_fp64_reference_on_the_sensor_config_matrix(name):
+    """The comparison above, with its TOL, its band and its cap of 1 % exempt cells, on every entry of sensor_configs.MATRIX: a 24 x 40
+    grid in the heading mode at margin 0.25 towards every source class, a 24 x 40 world grid at margin 0.4 about the entry's own arena,
+    the source sets taken in turn, and the library's default spec, whose extent, blocking and sources are derived from the config
+    (flagrun's open field has no walls).  On the entry's hostile states the field equals, bit for bit, that of the clean twin."""
+    cfg, state, items, aux = scfg.shard(name)
+    specs = [(fc.spec_of((24, 40), F.HRL_VIEW_EGO_HEADING, 0.25, ALL_SOURCES, kind=cfg), ALL_SOURCES),
+             (fc.spec_of((24, 40), F.HRL_VIEW_WORLD, 0.4, F.ROBOT, kind=cfg, centre=fc.WORLD_CENTRE), None), (F.default_spec(cfg), F.default_spec(cfg).sources)]
+    worst, exempt_worst, rounds_worst = compare_with_the_reference(cfg, state, items, aux, specs, name)
+    print(f'{name}: worst |dist - reference| {worst:.3g} m, most exempt cells {100 * exempt_worst:.2f} %, most Jacobi rounds {rounds_worst}')
+    for spec, _ in specs[:2]:
+        spec = spec.copy()
+        spec.sources = ALL_SOURCES
+        for s, it, a, cs, cit, ca, far, blind in scfg.hostile(name, fc.hostile):
+            got = fc.field_host(cfg, s, it, a, spec)
+            want = fc.field_host(fc.far_targets(cfg) if far else cfg, cs, cit, ca, spec)
+            rows = [e for e in range(N) if e not in blind]
+            assert fc.same(fc.Field(*(x[rows] for x in got)), fc.Field(*(x[rows] for x in want))), (name, spec.mode)
+            if spec.mode != F.HRL_VIEW_WORLD:
+                assert all((got.parent[e] == F.BLOCKED).all() for e in blind)
 
 
 @pytest.mark.parametrize('kind', (K.HRL_ANT_MAZE, K.HRL_ANT_GATHER, K.HRL_ANT_FLAGRUN))

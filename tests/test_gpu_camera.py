@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import camera_cases as cc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import camera_device as Cm
 from test_gpu_render import host_items, make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
@@ -66,6 +67,41 @@ def test_device_images_equal_the_host_build_bit_for_bit(kind):
                 assert same(dev, host) and bool(dev.seg[4].any()) == (eye_mode == Cm.HRL_EYE_GROUND)
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_images_equal_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: 16 x 8 (128 pixels: two waves idle)
+    and 64 x 48 in both frames and both eye modes, the eye heights, class sets, ranges and fields of view of camera_cases.sweep taken
+    in turn, on the shard and with the robots spread about the entry's arena, and the library's default spec; then the hostile states
+    (on the entries of 64 items: NaN and inf in the last item).  depth (as uint32), seg and rgb equal the host build of camera_core.h.
+    On the entries of 64 items the device shows an item of index 48 or more, on maze-12 the posts 8 and 11."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    codes, turn = set(), 0
+    for frame in cc.FRAMES:
+        for eye_mode in cc.EYE_MODES:
+            for size in ((16, 8), (64, 48)):
+                spec = cc.spec_of(size, frame, eye_mode, cc.EYE_HEIGHTS[turn % 3], cc.CLASS_SETS[(turn // 3 + turn) % 3], (30.0, 7.0)[turn % 2], cc.TANS[(turn // 2) % 2])
+                turn += 1
+                for s in (st, cc.spread(cfg, st)):
+                    dev, host = both(env, s, it, aux, spec)
+                    assert same(dev, host), (name, size, frame, eye_mode, spec.classes)
+                    codes |= set(np.unique(dev.seg.cpu().numpy() & 0xFFFF).tolist())
+    put(env, st, it, aux)
+    dev = env.camera()
+    assert same(dev, cc.camera_host(env.cfg, st, host_items(env, it), aux, Cm.default_spec(env.cfg))), (name, 'default')
+    codes |= set(np.unique(dev.seg.cpu().numpy() & 0xFFFF).tolist())
+    assert {Cm.HIT_NONE, Cm.HIT_GROUND} <= {c & 255 for c in codes}
+    spec = cc.spec_of((64, 48), Cm.HRL_SCAN_HEADING, Cm.HRL_EYE_TORSO, 0.6)
+    for s, i2, a, _, _, _, _, blind in scfg.hostile(name, cc.hostile):
+        dev, host = both(env, s, i2, a, spec)
+        assert same(dev, host), (name, 'hostile')
+        assert all(not bool(dev.seg[e].any()) for e in blind)
+    if scfg.many_items(cfg):
+        assert scfg.saw_a_late_item(sorted(codes))
+    if name == 'maze-12':
+        assert {Cm.HIT_TARGET | t << 8 for t in (8, 11)} <= codes
 
 
 def arena_of(spec, n, fill=0x7B):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import field_cases as fc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import field_device as F
 from test_gpu_render import host_items, make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
@@ -74,6 +75,31 @@ def test_device_field_equals_the_host_build_bit_for_bit(kind):
                         assert all(bool((dev.parent[e] == F.BLOCKED).all()) for e in blind)
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_field_equals_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: the three modes at 8 x 8 (64 cells)
+    and 24 x 40, margins 0 and 0.4 and the source sets taken in turn, on the shard and with the robots spread about the entry's arena,
+    and the library's default spec; then the hostile states (on the entries of 64 items: NaN and inf in the last item): dist as uint32
+    and parent as bytes equal the host build of field_core.h."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    turn = 0
+    for mode in fc.MODES:
+        for size in ((8, 8), (24, 40)):
+            for s in (st, fc.spread(cfg, st)):
+                spec = fc.spec_of(size, mode, (0.0, 0.4)[turn % 2], fc.SOURCE_SETS[(4 * turn + 2) % len(fc.SOURCE_SETS)], kind=cfg, centre=fc.WORLD_CENTRE)
+                turn += 1
+                dev, host = both(env, s, it, aux, spec)
+                assert same(dev, host), (name, mode, size, spec.margin, spec.sources)
+    put(env, st, it, aux)
+    assert same(env.field(), fc.field_host(env.cfg, st, host_items(env, it), aux, F.default_spec(env.cfg))), (name, 'default')
+    for mode in (F.HRL_VIEW_WORLD, F.HRL_VIEW_EGO_HEADING):
+        spec = fc.spec_of((24, 40), mode, 0.4, ALL_SOURCES, kind=cfg)
+        for s, i2, a, _, _, _, _, _ in scfg.hostile(name, fc.hostile):
+            dev, host = both(env, s, i2, a, spec)
+            assert same(dev, host), (name, mode, 'hostile')
 
 
 def test_source_and_blocking_subsets_and_the_default_spec():

@@ -11,6 +11,7 @@ import torch
 import field_cases as fc
 import frontier_cases as xc
 import see_cases as vc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import frontier_device as X
 from hrl_pybullet_envs_amd import see_device as V
@@ -75,6 +76,36 @@ def test_device_map_equals_the_host_build_bit_for_bit(kind):
                     assert all(int(dev.cell[e]) == -1 for e in blind)
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_map_equals_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: 8 x 8 (one wave of cells) and
+    24 x 40 x both meanings of `unknown`, the source sets and the margins taken in turn, on the shard and with the robots spread about
+    the entry's arena, with real and dirty memories, and the library's default spec; then the hostile states (on the entries of 64
+    items: NaN and inf in the last item).  All seven outputs equal the host build of frontier_core.h."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    turn, edges = 0, 0
+    for size in ((8, 8), (24, 40)):
+        for unknown in xc.UNKNOWNS:
+            for s, which in ((st, 'real'), (xc.spread(cfg, st), 'dirty')):
+                spec = xc.spec_of(size, xc.MARGINS[turn % 3], xc.SOURCE_SETS[(7 * turn) % 31], unknown, kind=cfg)
+                turn += 1
+                seen = xc.memory(which, env.cfg, np.array(s), host_items(env, it), aux, spec, turn)
+                dev, host = both(env, s, it, aux, spec, seen)
+                assert same(dev, host), (name, size, unknown, which, turn)
+                edges += int(host.count.sum())
+    assert edges > 100
+    spec = X.default_spec(env.cfg)
+    dev, host = both(env, st, it, aux, spec, xc.memory('real', env.cfg, np.array(st), host_items(env, it), aux, spec, 2))
+    assert same(dev, host), (name, 'default')
+    spec = xc.spec_of((24, 40), 0.25, X.EDGE | xc.CLASS_SOURCES, X.OPTIMISTIC, kind=cfg)
+    seen = xc.memory('dirty', env.cfg, np.array(st), None, aux, spec, 3)
+    for s, i2, a, _, _, _, _, blind in scfg.hostile(name, xc.hostile):
+        dev, host = both(env, s, i2, a, spec, seen)
+        assert same(dev, host), (name, 'hostile')
+        assert all(int(dev.cell[e]) == -1 for e in blind)
 
 
 def test_the_chain_over_real_steps():

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import probe_cases as pc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import probe_device as P
 from test_gpu_render import host_items, make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
@@ -69,6 +70,43 @@ def test_device_probes_equal_the_host_build_bit_for_bit(kind):
                 assert same(dev, host), (kind, frame, 'hostile')
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_probes_equal_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: 1 point (a block of 64 threads, which
+    stages a record of 96 or 128 floats in two trips), 65 and 512 points in the three frames, margins 0 and 0.4 in turn, and the
+    library's default spec on the shard and with the robots spread about the entry's arena; 1 and 65 points on the hostile states (on
+    the entries of 64 items: NaN and inf in the last item) and hostile points: every float as uint32 and every int32 equal the host
+    build of probe_core.h.  On the entries of 64 items the device names an item of index 48 or more, on maze-12 the targets 8 and 11."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    codes, turn = set(), 0
+    for n in (1, 65, 512):
+        for frame in pc.FRAMES:
+            for s in (st, pc.spread(cfg, st)):
+                spec = pc.spec_of(n, frame, pc.MARGINS[turn % 2])
+                turn += 1
+                pts = pc.draw_points(cfg, s, frame, n, pc.seed_of(cfg, spec))
+                dev, host = both(env, s, it, aux, spec, pts)
+                assert same(dev, host), (name, n, frame, spec.margin)
+                codes |= set(np.unique(dev.nearest.cpu().numpy()).tolist()) | set(np.unique(dev.blocker.cpu().numpy()).tolist())
+    pts = pc.draw_points(cfg, st, P.HRL_PROBE_WORLD, 64, 13)
+    put(env, st, it, aux)
+    assert same(env.probe(dev_points(pts)), pc.probe_host(env.cfg, st, host_items(env, it), aux, P.default_spec(env.cfg, 'world', 64), pts)), (name, 'default')
+    for n in (1, 65):
+        spec = pc.spec_of(n, P.HRL_PROBE_HEADING, 0.4)
+        pts = pc.hostile_points(pc.draw_points(cfg, st, spec.frame, 65, 5))[0][:, 65 - n:].copy()
+        for s, i2, a, _, _, _, _, _ in scfg.hostile(name, pc.hostile):
+            dev, host = both(env, s, i2, a, spec, pts)
+            assert same(dev, host), (name, n, 'hostile')
+    pts = pc.hostile_points(pc.draw_points(cfg, st, P.HRL_PROBE_EGO, 65, 5))[0]
+    dev, host = both(env, st, it, aux, pc.spec_of(65, P.HRL_PROBE_EGO, 0.0), pts)
+    assert same(dev, host), (name, 'hostile points')
+    if scfg.many_items(cfg):
+        assert scfg.saw_a_late_item(sorted(codes))
+    if name == 'maze-12':
+        assert {P.HIT_TARGET | t << 8 for t in (8, 11)} <= codes
 
 
 def test_class_subsets_and_the_default_spec():

@@ -10,6 +10,7 @@ import torch
 import field_cases as fc
 import probe_cases as pc
 import route_cases as rt
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import field_device as F
 from hrl_pybullet_envs_amd import route_device as R
@@ -84,6 +85,39 @@ def test_device_routes_equal_the_host_build_bit_for_bit(kind):
                 assert bool((dev.count[:, list(blank) + list(huge)] == 0).all())
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_routes_equal_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: 16 x 16 grids in the three modes
+    with 1 and 64 starts, K = 2 and 32, the frames and the source sets taken in turn, on the shard and with the robots spread about the
+    entry's arena, starts = None once per mode, and the library's default spec; then the hostile states (on the entries of 64 items:
+    NaN and inf in the last item).  cells and count as integers, waypoints and length as uint32 equal the host build of route_core.h."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    turn, routes = 0, 0
+    for mode in rt.MODES:
+        for p in (1, 64):
+            for s in (st, fc.spread(cfg, st)):
+                frame, k = rt.FRAMES[turn % 3], (2, 32)[(turn // 2) % 2]
+                fspec = fc.spec_of((16, 16), mode, 0.25, fc.SOURCE_SETS[(4 * turn + 2) % len(fc.SOURCE_SETS)], kind=cfg, centre=fc.WORLD_CENTRE)
+                turn += 1
+                spec = rt.spec_of(fspec, frame, p, k)
+                starts, _ = rt.draw_starts(cfg, s, fspec, frame, p, 11 * turn + scfg.seed_of(name))
+                dev, host = both(env, s, it, aux, spec, starts)
+                assert same(dev, host), (name, mode, p, frame, k, fspec.sources)
+                routes += int((host.count > 0).sum())
+        dev, host = both(env, s, it, aux, rt.spec_of(fspec, frame, 1, k), None)
+        assert same(dev, host), (name, mode, 'robot')
+    assert routes > 0
+    put(env, st, it, aux)
+    assert same(env.route(), rt.route_host(env.cfg, st, host_items(env, it), aux, R.default_spec(env.cfg), None)), (name, 'default')
+    fspec = fc.spec_of((16, 16), F.HRL_VIEW_EGO_HEADING, 0.4, ALL_SOURCES, kind=cfg)
+    spec = rt.spec_of(fspec, R.HRL_PROBE_HEADING, 8, 7)
+    starts, _ = rt.draw_starts(cfg, st, fspec, R.HRL_PROBE_HEADING, 8, 5)
+    for s, i2, a, _, _, _, _, _ in scfg.hostile(name, fc.hostile):
+        dev, host = both(env, s, i2, a, spec, starts)
+        assert same(dev, host), (name, 'hostile')
 
 
 def test_the_routes_follow_the_chain_of_the_devices_own_field():

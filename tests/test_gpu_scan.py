@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import scan_cases as sc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import scan_device as S
 from test_gpu_render import host_items, make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
@@ -59,6 +60,34 @@ def test_device_scan_equals_the_host_build_bit_for_bit(kind):
                 assert same(dev, host), (kind, frame, 'hostile')
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_scan_equals_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: 1 ray (a block of 64 threads, which
+    stages a record of 96 or 128 floats in two trips), 65 and 512 rays in both frames and the library's default spec on the shard, 1
+    and 65 rays on the hostile states (on the entries of 64 items: NaN and inf in the last item): `range` as uint32 and `hit` equal the
+    host build of scan_core.h.  On the entries of 64 items the device reports an item of index 48 or more, on maze-12 the targets 8
+    and 11."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    hits = []
+    for spec in [sc.spec_of(n, f, r) for n, r in ((1, 20.0), (65, 6.0), (512, 20.0)) for f in sc.FRAMES] + [S.default_spec(env.cfg)]:
+        dev, host = both(env, st, it, aux, spec)
+        assert same(dev, host), (name, spec.n_rays, spec.frame, spec.max_range)
+        hits.append(dev[1].cpu().numpy())
+    put(env, st, it, aux)
+    assert same(env.scan(), sc.scan_host(env.cfg, st, host_items(env, it), aux, S.default_spec(env.cfg))), (name, 'default')
+    assert same(env.scan(sc.spec_of(1, S.HRL_SCAN_WORLD, 20.0, S.FOOD | S.POISON | S.TARGET)),
+                sc.scan_host(env.cfg, st, host_items(env, it), aux, sc.spec_of(1, S.HRL_SCAN_WORLD, 20.0, S.FOOD | S.POISON | S.TARGET))), (name, 'one ray, items alone')
+    for s, i2, a, _, _, _, _, _ in scfg.hostile(name, sc.hostile):
+        for n in (1, 65):
+            dev, host = both(env, s, i2, a, sc.spec_of(n, S.HRL_SCAN_HEADING, 20.0))
+            assert same(dev, host), (name, n, 'hostile')
+    if scfg.many_items(cfg):
+        assert all(scfg.saw_a_late_item(hits[4][e]) for e, _, _ in scfg.NEAR_ITEMS)
+    if name == 'maze-12':
+        assert {S.HIT_TARGET | t << 8 for t in (8, 11)} <= set(hits[4].ravel().tolist())
 
 
 def test_class_subsets_and_the_default_spec():

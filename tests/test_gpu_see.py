@@ -9,6 +9,7 @@ import torch
 
 import field_cases as fc
 import see_cases as vc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import see_device as V
 from test_gpu_render import host_items, make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
@@ -80,6 +81,36 @@ def test_device_map_equals_the_host_build_bit_for_bit(kind):
                     assert all(not bool(dev.visible[e].any()) for e in blind)
     finally:
         put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_device_map_equals_the_host_build_on_the_sensor_config_matrix(name):
+    """Every entry of sensor_configs.MATRIX at N = 5, its shard's records written into the device env: the three modes at 8 x 8 (one wave
+    of cells) and 24 x 40, the three specs of see_cases.sweep_specs taken in turn, on the shard and with the robots spread about the
+    entry's arena, and the library's default spec; then the hostile states (on the entries of 64 items: NaN and inf in the last item).
+    visible, seen and fresh equal the host build of see_core.h."""
+    cfg, st, it, aux = scfg.shard(name)
+    env = scfg.device_env(name)
+    turn, lit = 0, 0
+    for mode in vc.MODES:
+        for size in ((8, 8), (24, 40)):
+            for s in (st, vc.spread(cfg, st)):
+                spec = vc.sweep_specs(size, mode, cfg)[turn % 3]
+                turn += 1
+                dev, host = both(env, s, it, aux, spec, turn)
+                assert same(dev, host), (name, mode, size, turn)
+                lit += int(host.visible.sum())
+    assert lit > 100
+    dev, host = both(env, st, it, aux, V.default_spec(env.cfg), 1)
+    assert same(dev, host), (name, 'default')
+    assert np.array_equal(env.see().visible.cpu().numpy(), host.visible), (name, 'default, none given')
+    for mode in (V.HRL_VIEW_WORLD, V.HRL_VIEW_EGO_HEADING):
+        spec = vc.spec_of((24, 40), mode, V.ALL, slack=0.1, kind=cfg)
+        for s, i2, a, _, _, _, _, blind in scfg.hostile(name, fc.hostile):
+            turn += 1
+            dev, host = both(env, s, i2, a, spec, turn)
+            assert same(dev, host), (name, mode, 'hostile')
+            assert all(not bool(dev.visible[e].any()) for e in blind)
 
 
 def test_memory_over_real_steps():

@@ -15,6 +15,7 @@ import pytest
 
 import orc
 import probe_cases as pc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import probe_device as P
 from test_render_host import shard   # the oracle's shards of 5 envs after reset + 30 random steps: computed once, read-only
@@ -38,19 +39,29 @@ def test_host_build_equals_the_fp64_reference(kind):
     clearance 2.9e-6 m, path 3.2e-6 m (an ulp of 16 m is 1.9e-6 m) and sight 8.9e-6 m (a segment grazing the flagrun goal's disc; 3.2e-6 m
     elsewhere); asserted at 4 x that: 1.2e-5, 1.3e-5 and 3.6e-5 m, under the ceiling of 1e-4 m."""
     cfg, state, items, aux = shard(kind)
+    worst, vias, _ = compare_with_the_reference(cfg, state, items, aux, pc.all_specs(), kind)
+    print(f'kind {kind}: worst errors {worst}')
+    if pc.is_maze(cfg):   # the sweep goes round the box
+        assert {0, 1, 2, 5} <= vias, vias
+
+
+def compare_with_the_reference(cfg, state, items, aux, specs, tag):
+    """The comparison of test_host_build_equals_the_fp64_reference on the given states, their hand-made poses and with the robots spread
+    about the arena; returns (the worst error per output in metres, the values of `via` met, every code of `nearest` and `blocker` met)."""
     worst = dict(clearance=0.0, sight=0.0, path=0.0)
-    vias = set()
-    for spec in pc.all_specs():
+    vias, codes = set(), set()
+    for spec in specs:
         runs = []
         for st in (state, pc.hand_made(cfg, state), pc.spread(cfg, state)):
             pts = pc.draw_points(cfg, st, spec.frame, spec.n_points, pc.seed_of(cfg, spec))
             runs.append((st, pts))
-        where = (kind, spec.n_points, spec.frame, spec.margin)
+        where = (tag, spec.n_points, spec.frame, spec.margin)
         results = []
         for st, pts in runs:
             got = pc.probe_host(cfg, st, items, aux, spec, pts)
             results.append(pc.compare(cfg, st, items, aux, spec, pts, got, TOL))
             vias |= set(np.unique(got.via))
+            codes |= set(np.unique(got.nearest).tolist()) | set(np.unique(got.blocker).tolist())
         for name in ('nearest', 'blocker', 'via0'):   # on the reference alone, before the build is looked at
             ex = sum(r['exempt_' + name].sum() for r in results)
             assert ex <= 0.01 * sum(r['exempt_' + name].size for r in results), (where, name, ex)
@@ -60,9 +71,33 @@ def test_host_build_equals_the_fp64_reference(kind):
             for name in worst:
                 worst[name] = max(worst[name], float(r['err_' + name].max()))
                 assert r['err_' + name].max() <= TOLS[name], (where, name, r['err_' + name].max())
-    print(f'kind {kind}: worst errors {worst}')
-    if pc.is_maze(cfg):   # the sweep goes round the box
-        assert {0, 1, 2, 5} <= vias, vias
+    return worst, vias, codes
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_host_build_equals_the_fp64_reference_on_the_sensor_config_matrix(name):
+    """The comparison above, with its tolerances and its cap of 1 % exempt points, on every entry of sensor_configs.MATRIX: 65 points in
+    the heading frame at margin 0.4, 512 in the world frame at margin 0 (drawn from the entry's own arena grown by 1 m) and the
+    library's default spec at 37 points.  On the entry's hostile states the probes equal, bit for bit, those of the clean twin and a
+    robot at a non-finite place gets the blank answers.  On the entries of 64 items an item of index 48 or more is some point's
+    nearest shape or blocker; on maze-12 the targets 8 and 11 are."""
+    cfg, state, items, aux = scfg.shard(name)
+    specs = [pc.spec_of(65, P.HRL_PROBE_HEADING, 0.4), pc.spec_of(512, P.HRL_PROBE_WORLD, 0.0), P.default_spec(cfg, 'world', 37)]
+    worst, _, codes = compare_with_the_reference(cfg, state, items, aux, specs, name)
+    print(f'{name}: worst errors {worst}')
+    for spec in specs[:2]:
+        pts = pc.draw_points(cfg, state, spec.frame, spec.n_points, 5)
+        for s, it, a, cs, cit, ca, far, blind in scfg.hostile(name, pc.hostile):
+            got = pc.probe_host(cfg, s, it, a, spec, pts)
+            want = pc.probe_host(pc.far_targets(cfg) if far else cfg, cs, cit, ca, spec, pts)
+            rows = [e for e in range(N) if e not in blind]
+            for x, y in zip(got, want):
+                assert np.array_equal(x[rows].view(np.uint32), y[rows].view(np.uint32)), (name, spec.n_points)
+            assert pc.is_blank(got, rows=blind)
+    if scfg.many_items(cfg):
+        assert scfg.saw_a_late_item(sorted(codes)), sorted(codes)
+    if name == 'maze-12':
+        assert {P.HIT_TARGET | t << 8 for t in (8, 11)} <= codes
 
 
 def maze_env(robots, n=None):

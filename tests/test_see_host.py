@@ -15,6 +15,7 @@ import field_cases as fc
 import orc
 import probe_cases as pc
 import see_cases as vc
+import sensor_configs as scfg
 from hrl_pybullet_envs_amd import _capi as K
 from hrl_pybullet_envs_amd import field_device as F
 from hrl_pybullet_envs_amd import probe_device as P
@@ -43,27 +44,56 @@ def test_host_build_equals_the_fp64_reference(kind):
     first spec; 12 and 9 in the gather kinds under it), at most 5 cells under the second spec, at most 1 under the third."""
     cfg, state, items, aux = shard(kind)
     for k in range(3):
-        runs = []
-        exempt_cells = cells = seen_cells = 0
-        for mode in vc.MODES:
-            for size in vc.SIZES:
-                spec = vc.sweep_specs(size, mode, kind)[k]
-                for label, st in states_of(cfg, state):
-                    refs = [vc.stable_reference(cfg, st[e], None if items is None else items[e], aux[e], spec) for e in range(N)]
-                    exempt_cells += sum(int(x.sum()) for _, x in refs)
-                    cells += N * size[0] * size[1]
-                    runs.append((mode, size, label, spec, st, refs))
-        share = exempt_cells / cells
-        print(f'kind {kind} spec {k}: {exempt_cells} of {cells} cells exempt ({100 * share:.3f} %)')
-        assert share <= EXEMPT_CAP, (kind, k, share)   # on the reference alone
-        for mode, size, label, spec, st, refs in runs:
-            got = vc.see_host(cfg, st, items, aux, spec).visible
-            assert got.dtype == np.uint8 and got.max() <= 1
-            for e, (ref, exempt) in enumerate(refs):
-                wrong = (got[e].astype(bool) != ref) & ~exempt
-                assert not wrong.any(), (kind, k, mode, size, label, e, np.argwhere(wrong)[:5].tolist())
-                seen_cells += int(ref.sum())
+        specs = [vc.sweep_specs(size, mode, kind)[k] for mode in vc.MODES for size in vc.SIZES]
+        seen_cells, cells = compare_with_the_reference(cfg, state, items, aux, specs, f'kind {kind} spec {k}')
         assert 0 < seen_cells and (seen_cells < cells or k == 0), (kind, k)   # both verdicts occur (an arena with nothing in it hides nothing all round)
+
+
+def compare_with_the_reference(cfg, state, items, aux, specs, tag):
+    """The comparison of test_host_build_equals_the_fp64_reference of one group of specs (the cap of exempt cells is the group's) on the
+    given states, their hand-made poses and with the robots spread about the arena; returns (the cells the reference sees, all cells)."""
+    runs = []
+    exempt_cells = cells = seen_cells = 0
+    for spec in specs:
+        for label, st in states_of(cfg, state):
+            refs = [vc.stable_reference(cfg, st[e], None if items is None else items[e], aux[e], spec) for e in range(N)]
+            exempt_cells += sum(int(x.sum()) for _, x in refs)
+            cells += N * spec.width * spec.height
+            runs.append((label, spec, st, refs))
+    share = exempt_cells / cells
+    print(f'{tag}: {exempt_cells} of {cells} cells exempt ({100 * share:.3f} %)')
+    assert share <= EXEMPT_CAP, (tag, share)   # on the reference alone
+    for label, spec, st, refs in runs:
+        got = vc.see_host(cfg, st, items, aux, spec).visible
+        assert got.dtype == np.uint8 and got.max() <= 1
+        for e, (ref, exempt) in enumerate(refs):
+            wrong = (got[e].astype(bool) != ref) & ~exempt
+            assert not wrong.any(), (tag, spec.mode, (spec.width, spec.height), label, e, np.argwhere(wrong)[:5].tolist())
+            seen_cells += int(ref.sum())
+    return seen_cells, cells
+
+
+@pytest.mark.parametrize('name', scfg.NAMES)
+def test_host_build_equals_the_fp64_reference_on_the_sensor_config_matrix(name):
+    """The comparison above, with its cap of 1 % exempt cells per spec, on every entry of sensor_configs.MATRIX: everything occludes on a
+    24 x 40 grid in the heading mode with a slack of one cell, walls and the box occlude a field of view of 120 degrees out to 6 m on a
+    24 x 40 world grid about the entry's own arena, and the library's default spec, whose extent is derived from the config (flagrun's
+    open field has no walls: nothing is hidden there).  On the entry's hostile states the map equals that of the clean twin and a
+    robot without a finite place sees nothing."""
+    cfg, state, items, aux = scfg.shard(name)
+    specs = [vc.sweep_specs((24, 40), V.HRL_VIEW_EGO_HEADING, cfg)[0], vc.sweep_specs((24, 40), V.HRL_VIEW_WORLD, cfg)[1], V.default_spec(cfg)]
+    for k, spec in enumerate(specs):
+        seen_cells, cells = compare_with_the_reference(cfg, state, items, aux, [spec], f'{name} spec {k}')
+        assert 0 < seen_cells and (seen_cells < cells or k != 1), (name, k)   # a field of view hides something in every arena
+    for spec in specs[:2]:
+        spec = spec.copy()
+        spec.occluders, spec.slack = V.ALL, 0.1
+        for s, it, a, cs, cit, ca, far, blind in scfg.hostile(name, fc.hostile):
+            got = vc.see_host(cfg, s, it, a, spec).visible
+            want = vc.see_host(fc.far_targets(cfg) if far else cfg, cs, cit, ca, spec).visible
+            rows = [e for e in range(N) if e not in blind]
+            assert np.array_equal(got[rows], want[rows]), (name, spec.mode)
+            assert (got[list(blind)] == 0).all() and want.any()
 
 
 @pytest.mark.parametrize('kind', vc.KINDS)
