@@ -3,8 +3,9 @@ hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_re
 (the batched range scanner, include/hrl_scan.h), hrl_pybullet_envs_amd/libhrl_probe_hip.so (the batched point probes,
 include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h),
 hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h), hrl_pybullet_envs_amd/libhrl_see_hip.so (the
-batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map, include/hrl_frontier.h) and
-hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h).
+batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map, include/hrl_frontier.h),
+hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h) and
+hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -31,6 +32,8 @@ SEE = ('see', 'libhrl_see_hip.so', 'see_hip.hip', 'see_core.h', 'hrl_see.h')
 FRONTIER = ('frontier', 'libhrl_frontier_hip.so', 'frontier_hip.hip', 'frontier_core.h', 'hrl_frontier.h')
 # The first-person camera stands on the scanner's chain alone (render, scan): the scanner's table plus a z-interval per slot.
 CAMERA = ('camera', 'libhrl_camera_hip.so', 'camera_hip.hip', 'camera_core.h', 'hrl_camera.h')
+# The link states stand on no other sensor: the step's own kinematics (step_core.h, included) restated in a specification of their own.
+LINKS = ('links', 'libhrl_links_hip.so', 'links_hip.hip', 'links_core.h', 'hrl_links.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -125,8 +128,17 @@ def build_camera(force=False, verbose=False):
     return lib
 
 
+def build_links(force=False, verbose=False):
+    """The link states' library; returns its path.  It depends on its own three files, the shared launcher and the step's headers."""
+    _, lib, source, core, header = LINKS
+    lib = os.path.join(PKG, lib)
+    if force or _stale(lib, [source, core, 'sensor_launch.h'] + SOURCES[1:], ['hrl_envs.h', header]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The nine libraries; returns the step library's path."""
+    """The ten libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
@@ -135,10 +147,11 @@ def build(force=False, verbose=False):
     build_see(force, verbose)
     build_frontier(force, verbose)
     build_camera(force, verbose)
+    build_links(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS]:
         print(os.path.join(PKG, lib))

@@ -243,6 +243,13 @@ class BatchedGymEnv:
         (BatchedEnv.camera; camera_device.default_spec for other sizes, fields of view, eye heights and classes)."""
         return self._backend().camera(spec, mask, out)
 
+    def links_batch(self, spec=None, mask=None, out=None):
+        """The link states of EVERY env in one launch: Links(origin, com, quat, lin_vel, ang_vel [N, B, ...], site_pos, site_vel [N, S, 3])
+        on the env's device: where every body of each robot is and how it moves, and the spec's sites -- by default the four foot tips
+        (BatchedEnv.links; links_device.default_spec for the heading frame and other sites).  `robot.parts` / `robot.feet` read the same
+        launch one body at a time."""
+        return self._backend().links(spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

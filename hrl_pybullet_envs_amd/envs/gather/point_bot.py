@@ -28,5 +28,7 @@ class PointBot:
     body_rpy = property(lambda self: self._view.body_rpy if self._view else np.zeros(3))
     robot_body = property(lambda self: self._view.robot_body if self._view else None)   # upstream BodyPart of the cube: pose().xyz() / .rpy(), get_position(), speed()
 
+    parts = property(lambda self: self._view.parts if self._view else {})   # upstream `robot.parts`: the cube alone, from one links() launch (RobotView.parts)
+
     def alive_bonus(self, z, pitch):
         return 1                           # point_bot.py:73-74: cannot die

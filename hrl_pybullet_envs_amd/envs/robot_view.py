@@ -97,6 +97,62 @@ class BodyView:
         return self._r._out(self._r._state()[:, K.HRL_QVEL_OFF:K.HRL_QVEL_OFF + 3])
 
 
+class LinkPoseView:
+    """upstream robot_bases.Pose_Helper of one link of `robot.parts`"""
+
+    def __init__(self, part):
+        self._p = part
+
+    def xyz(self):
+        return self._p.get_position()
+
+    def rpy(self):
+        return self._p._out(quat_to_rpy(self._p._s['quat'][:, self._p._i]))
+
+    def orientation(self):
+        return self._p.get_orientation()
+
+
+class LinkView:
+    """upstream robot_bases.BodyPart of one link (`robot.parts[name]`, `robot.feet[i]`): a read-only view of link `index` in one snapshot of
+    BatchedEnv.links() -- position = the centre of mass (what pybullet's getLinkState()[0] is), orientation = the MJCF body frame
+    (quaternion x y z w; include/hrl_links.h on how that differs from pybullet's inertial frame), speed = the centre of mass's velocity.
+    Single env: numpy rows like the reference; batched: [N, ...]."""
+
+    def __init__(self, snapshot, index, single):
+        self._s, self._i, self._single = snapshot, index, single
+
+    def _out(self, a):
+        return a[0] if self._single else a
+
+    def pose(self):
+        return LinkPoseView(self)
+
+    def get_position(self):
+        return self._out(self._s['com'][:, self._i])
+
+    current_position = get_position
+
+    def get_orientation(self):
+        return self._out(self._s['quat'][:, self._i])
+
+    current_orientation = get_orientation
+
+    def get_pose(self):
+        return self._out(np.concatenate([self._s['com'][:, self._i], self._s['quat'][:, self._i]], 1))
+
+    def speed(self):
+        return self._out(self._s['lin_vel'][:, self._i])
+
+    def get_velocity(self):
+        """(linear, angular), as pybullet's getBaseVelocity / getLinkState(computeLinkVelocity=1) pair them"""
+        return self.speed(), self._out(self._s['ang_vel'][:, self._i])
+
+    def origin(self):
+        """the link frame's origin: the joint anchor"""
+        return self._out(self._s['origin'][:, self._i])
+
+
 _ANT_LO = np.deg2rad([-40.0, 30, -40, -100, -40, -100, -40, 30])   # assets/ant.xml:18-54, tree order
 _ANT_HI = np.deg2rad([40.0, 100, 40, -30, 40, -30, 40, 100])
 
@@ -108,6 +164,40 @@ class RobotView:
     @property
     def robot_body(self):
         return BodyView(self)
+
+    _PART_FIELDS = (('origin', 3), ('com', 3), ('quat', 4), ('lin_vel', 3), ('ang_vel', 3))
+
+    @property
+    def parts(self):
+        """upstream `robot.parts`: a dict name -> LinkView of every rigid body of the robot (links_device.NAMES: the ant's 13, the point bot's
+        cube), all of them views of ONE BatchedEnv.links() launch in the world frame and one copy to the host, taken when the property is
+        read (float64 numpy, like the other attributes)."""
+        import torch
+
+        from .. import links_device as Lk
+        env = self._e._backend()
+        n, b = env.num_envs, Lk.n_links(env.cfg)
+        spec = env._default_spec('links-parts', lambda: Lk.default_spec(env.cfg, 'world', ()))
+        buf = torch.empty(n * b * sum(w for _, w in self._PART_FIELDS), dtype=torch.float32, device=env.device)
+        views, at = {}, 0
+        for name, w in self._PART_FIELDS:   # one buffer, a contiguous run per tensor: one copy brings all five
+            views[name] = buf[at:at + n * b * w].view(n, b, w)
+            at += n * b * w
+        env.links(spec, out=Lk.Links(**views))
+        host = buf.double().cpu().numpy()
+        snap, at = {}, 0
+        for name, w in self._PART_FIELDS:
+            snap[name] = host[at:at + n * b * w].reshape(n, b, w)
+            at += n * b * w
+        return {name: LinkView(snap, i, self._e.num_envs == 1) for i, name in enumerate(Lk.NAMES(env.cfg))}
+
+    @property
+    def feet(self):
+        """upstream `robot.feet`: the four foot parts in foot_list order (front_left_foot, front_right_foot, left_back_foot, right_back_foot)"""
+        self._ant('feet')
+        from .. import links_device as Lk
+        parts = self.parts
+        return [parts[name] for name in Lk.FOOT_LIST]
 
     def _ant(self, what):
         if self._e._cfg.env_kind == K.HRL_POINT_GATHER:

@@ -349,6 +349,30 @@ class BatchedEnv:
         self._sensor_launch('_last_camera_mask', mask, lambda m, stream: Cm.camera(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
+    def links(self, spec=None, mask=None, out=None):
+        """The state of every rigid body of every env's robot: a namedtuple Links(origin, com, quat, lin_vel, ang_vel, site_pos, site_vel) on
+        this device, from ONE launch on the current stream (links_device.py, include/hrl_links.h).  B = 13 links for the ants (the torso,
+        per leg the hinged upper body and the foot, then the four jointless hip capsules: links_device.NAMES), 1 for the point bot.  origin
+        [N, B, 3] = the link frame's origin, the joint anchor; com [N, B, 3] = the centre of mass, what the reference's
+        `parts[name].get_position()` answers (links_device.tip: the capsule's far end); quat [N, B, 4] = the body frame (x, y, z, w);
+        lin_vel / ang_vel [N, B, 3] = the velocity of the centre of mass and the angular velocity; site_pos / site_vel [N, S, 3] = the
+        spec's sites, points fixed to links (by default the four foot tips).  `spec`: an hrl_links_spec
+        (links_device.default_spec(cfg, frame, sites)); None = world frame, the default sites.  In the 'heading' frame positions are
+        relative to the torso and every vector is turned by minus the heading.  Envs with mask[i] == 0 keep what `out` holds (zeros in
+        fresh tensors).  `out`: a Links of tensors to reuse; a None member is not computed.  The states are of the state tensor as it is;
+        nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import links_device as Lk
+        if spec is None:
+            spec = self._default_spec('links', lambda: Lk.default_spec(self.cfg))
+        if out is None:
+            if not Lk.sized(spec):   # (the library refuses it too; no tensor can be shaped after it)
+                raise ValueError(f'spec.n_sites must be within 0..{Lk.MAX_SITES}, got {spec.n_sites}')
+            out = Lk.Links(*(self._fresh(mask, shape, dtype) if shape[0] else None for shape, (_, dtype) in zip(Lk.shapes(self.cfg, spec), Lk.FIELDS)))
+        else:
+            Lk.check_out(out, self.num_envs, self.cfg, spec, self.device)
+        self._sensor_launch('_last_links_mask', mask, lambda m, stream: Lk.links(self.cfg, self._bufs_ref, spec, m, out, stream))
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
