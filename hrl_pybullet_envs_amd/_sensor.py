@@ -1,5 +1,8 @@
-"""What the bindings of the sensor libraries share (render_device.py, scan_device.py, probe_device.py, field_device.py, route_device.py, see_device.py, frontier_device.py, camera_device.py): the base of their
-spec records, the loader of a library, the check of the tensors handed in as `out=`, and the record of output pointers."""
+"""What the bindings of the nine sensor libraries share (render_device.py, scan_device.py, probe_device.py, field_device.py, route_device.py,
+see_device.py, frontier_device.py, camera_device.py, links_device.py): the base of their spec records, the loader of a library, the checks of
+the tensors handed in (`out=`, points), and -- for the seven whose outputs are a record of optional members (all but render and scan) -- the
+namedtuple and the ctypes record made from FIELDS, the one check of `out=` and the launch."""
+import collections
 import ctypes as C
 import os
 
@@ -51,12 +54,12 @@ def loader(path, symbols, name, what, argtypes):
     return lib, check
 
 
-def check_tensors(tensors, label, fields, shape, device, align, optional=False):
-    """Every one of `tensors` is a contiguous tensor of `shape` on `device`, of the dtype of its entry in `fields` ((name, dtype), ...), its
-    address a multiple of `align` bytes.  The messages call it label + name.  optional: a None is skipped, but at least one must be given.
-    (One loop for all of them: this runs before every launch that is handed `out=`.)"""
+def check_tensors(tensors, label, fields, shapes, device, align, optional=False):
+    """Every one of `tensors` is a contiguous tensor on `device`, of the dtype of its entry in `fields` ((name, dtype), ...) and the shape of
+    its entry in `shapes`, its address a multiple of `align` bytes.  The messages call it label + name.  optional: a None is skipped, but at
+    least one must be given.  (One loop for all of them: this runs before every launch that is handed `out=`.)"""
     none = optional
-    for (name, dtype), t in zip(fields, tensors):
+    for (name, dtype), shape, t in zip(fields, shapes, tensors):
         if t is None and optional:
             continue
         none = False
@@ -73,6 +76,50 @@ def check_tensors(tensors, label, fields, shape, device, align, optional=False):
     return tensors
 
 
+def check_points(points, name, most, n, device):
+    """An input of points (`points` of probe(), `starts` of route()): float32, contiguous [n, P, 2] with 1 <= P <= most, on `device`."""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
+        raise TypeError(f'{name} must be a torch.float32 tensor, got {getattr(points, "dtype", type(points))}')
+    if points.dim() != 3 or points.shape[0] != n or points.shape[2] != 2 or not 1 <= points.shape[1] <= most or not points.is_contiguous():
+        raise ValueError(f'{name} must be contiguous [{n}, P, 2] with 1 <= P <= {most}, got {tuple(points.shape)}')
+    if points.device != device:
+        raise ValueError(f'{name} live on {points.device}, the env on {device}')
+    return points
+
+
+def out_types(name, record, fields, module):
+    """(namedtuple `name` whose members default to None, ctypes Structure `record` of one c_void_p per member) of `fields`
+    ((name, dtype), ...) for the binding `module` (its __name__)."""
+    names = [f for f, _ in fields]
+    kind = collections.namedtuple(name, names, defaults=(None,) * len(names), module=module)
+    return kind, type(record, (C.Structure,), {'_fields_': [(f, C.c_void_p) for f in names], '__module__': module})
+
+
+def check_out(kind, module, fields, shapes, out, device, distinct=False, note='a None member is skipped'):
+    """`out=` of a record-style sensor: a `kind` (a namedtuple of binding `module`, 'links_device') whose members are None (skipped) or
+    contiguous, 4-byte aligned tensors of the member's dtype (`fields`) and shape (its entry in `shapes`, N included) on `device`.  In this
+    order: the type; the members in the order of `fields`, so the first offending one is named; at least one must be given; then, if
+    `distinct`, no two of them (that hold anything) may be the same memory."""
+    if not isinstance(out, kind):
+        raise TypeError(f'out must be a {module}.{kind.__name__} ({note})')
+    check_tensors(out, 'out.', fields, shapes, device, 4, optional=True)
+    if distinct:
+        given = [(name, t) for (name, _), t in zip(fields, out) if t is not None]
+        for k, (a, x) in enumerate(given):
+            for b, y in given[k + 1:]:
+                if x.data_ptr() == y.data_ptr() and x.numel() and y.numel():
+                    raise ValueError(f'out.{a} and out.{b} must not be the same memory')
+    return out
+
+
 def out_record(record, fields, out):
     """The ctypes record of output pointers (`record`: a Structure of one c_void_p per field) of the namedtuple `out`; None stays NULL."""
     return record(**{name: (None if t is None else t.data_ptr()) for (name, _), t in zip(fields, out)})
+
+
+def launch(check, entry, record, fields, cfg, bufs_ref, spec, inputs, out, stream):
+    """One launch of a record-style sensor: entry(cfg, buffers, spec, *inputs, the record of `out`'s pointers, stream), the library's
+    hrl_<x>; `inputs` are the pointers between the spec and the outputs (the mask, and before it points, starts, clear or seen)."""
+    o = out_record(record, fields, out)
+    check(entry(C.byref(cfg), bufs_ref, C.byref(spec), *inputs, C.byref(o), stream))
+    return out

@@ -5,7 +5,6 @@ in HBM, from one kernel launch.
 
 Like the other sensors', the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a missing library is
 an error."""
-import collections
 import ctypes as C
 import math
 import os
@@ -28,9 +27,8 @@ EYES = {'ground': HRL_EYE_GROUND, 'torso': HRL_EYE_TORSO}
 RGB_SKY = (150, 200, 255)   # HRL_RGB_SKY
 MIN_WIDTH, MIN_HEIGHT, MAX_SIZE = 16, 8, 128   # HRL_CAMERA_MIN_WIDTH, _MIN_HEIGHT, _MAX_SIZE: multiples of 16 and of 8
 
-Camera = collections.namedtuple('Camera', 'depth seg rgb')
-Camera.__new__.__defaults__ = (None,) * 3
 FIELDS = (('depth', torch.float32), ('seg', torch.int32), ('rgb', torch.uint8))
+Camera, hrl_camera_out = _sensor.out_types('Camera', 'hrl_camera_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_CAMERA_LIB') or os.path.join(_PKG, 'libhrl_camera_hip.so')
@@ -40,10 +38,6 @@ SYMBOLS = ['hrl_camera_default_spec', 'hrl_camera', 'hrl_camera_last_error']   #
 class hrl_camera_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('frame', C.c_int32), ('eye_mode', C.c_int32), ('eye_height', C.c_float),
                 ('tan_half_h', C.c_float), ('tan_half_v', C.c_float), ('max_range', C.c_float), ('classes', C.c_uint32)]
-
-
-class hrl_camera_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_camera', 'the batched first-person camera has', {
@@ -95,39 +89,32 @@ def pixel_rays(spec):
     return u, s
 
 
-def shapes(spec):
-    """The shape after N of each member of Camera."""
-    return ((spec.height, spec.width), (spec.height, spec.width), (spec.height, spec.width, 3))
+def shapes(spec, lead=()):
+    """The shape after N of each member of Camera (with `lead` = (N,): the whole shape)."""
+    grid = lead + (spec.height, spec.width)
+    return (grid, grid, grid + (3,))
+
+
+def size_error(spec):
+    """Why no tensors can be shaped after the spec (the library refuses it too), or None."""
+    if MIN_WIDTH <= spec.width <= MAX_SIZE and MIN_HEIGHT <= spec.height <= MAX_SIZE:
+        return None
+    return f'spec.width must be within {MIN_WIDTH}..{MAX_SIZE} and spec.height within {MIN_HEIGHT}..{MAX_SIZE}, got {spec.width} x {spec.height}'
 
 
 def sized(spec):
-    """Whether tensors can be shaped after the spec (the library refuses the others too)."""
-    return MIN_WIDTH <= spec.width <= MAX_SIZE and MIN_HEIGHT <= spec.height <= MAX_SIZE
+    """Whether tensors can be shaped after the spec."""
+    return size_error(spec) is None
 
 
 def camera(cfg, bufs_ref, spec, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Camera; a None one is not computed) on the current device, from the buffer record behind
     `bufs_ref`."""
-    o = _sensor.out_record(hrl_camera_out, FIELDS, out)
-    check(lib().hrl_camera(C.byref(cfg), bufs_ref, C.byref(spec), mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_camera, hrl_camera_out, FIELDS, cfg, bufs_ref, spec, (mask_ptr,), out, stream)
 
 
 def check_out(out, n, spec, device):
     """`out=` of BatchedEnv.camera(): a Camera whose members are None (skipped) or contiguous, 4-byte aligned tensors of the member's
     dtype -- depth and seg [N, height, width], rgb [N, height, width, 3] -- on the env's device, no two of them the same memory; at least
     one must be given."""
-    if not isinstance(out, Camera):
-        raise TypeError('out must be a camera_device.Camera (a None member is skipped)')
-    given = []
-    for field, shape, t in zip(FIELDS, shapes(spec), out):
-        if t is not None:
-            _sensor.check_tensors((t,), 'out.', (field,), (n,) + shape, device, 4)
-            given.append((field[0], t))
-    if not given:
-        raise ValueError('out holds no tensor: at least one output must be given')
-    for k, (a, x) in enumerate(given):
-        for b, y in given[k + 1:]:
-            if x.data_ptr() == y.data_ptr():
-                raise ValueError(f'out.{a} and out.{b} must not be the same memory')
-    return out
+    return _sensor.check_out(Camera, 'camera_device', FIELDS, shapes(spec, (n,)), out, device, distinct=True)

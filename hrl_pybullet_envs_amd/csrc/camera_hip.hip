@@ -104,17 +104,9 @@ int hrl_camera(const hrl_config *cfg, const hrl_buffers *b, const hrl_camera_spe
     if (why.empty()) why = validate_out(out);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_camera: " + why);
     if (const int rc = check_record(LIB, b, "hrl_camera: null state or aux")) return rc;
-    const void *outs[3] = {out->depth, out->seg, out->rgb};
-    const char *names[3] = {"depth", "seg", "rgb"};
-    for (int i = 0; i < 3; ++i)
-        if (reinterpret_cast<uintptr_t>(outs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_camera: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (const int rc = check_device(LIB, ctx, outs[i], names[i])) return rc;
+    const Pointer ptrs[] = {{out->depth, "depth", 4}, {out->seg, "seg", 4}, {out->rgb, "rgb", 4}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 3, &d_dc)) return rc;
     hipLaunchKernelGGL(camera_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, mask, *out, *spec);
     return launched(LIB);

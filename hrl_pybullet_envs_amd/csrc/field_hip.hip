@@ -128,17 +128,9 @@ int hrl_field(const hrl_config *cfg, const hrl_buffers *b, const hrl_field_spec 
     if (why.empty()) why = validate_out(out);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_field: " + why);
     if (const int rc = check_record(LIB, b, "hrl_field: null state or aux")) return rc;
-    const void *outs[2] = {out->dist, out->parent};
-    const char *names[2] = {"dist", "parent"};
-    for (int i = 0; i < 2; ++i)
-        if (reinterpret_cast<uintptr_t>(outs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_field: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    for (int i = 0; i < 2; ++i)
-        if (const int rc = check_device(LIB, ctx, outs[i], names[i])) return rc;
+    const Pointer ptrs[] = {{out->dist, "dist", 4}, {out->parent, "parent", 4}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 2, &d_dc)) return rc;
     hipLaunchKernelGGL(field_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, mask, *out, *spec);
     return launched(LIB);

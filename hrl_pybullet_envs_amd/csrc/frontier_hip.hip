@@ -181,17 +181,10 @@ int hrl_frontier(const hrl_config *cfg, const hrl_buffers *b, const hrl_frontier
     if (why.empty()) why = validate_out(out, seen);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_frontier: " + why);
     if (const int rc = check_record(LIB, b, "hrl_frontier: null state or aux")) return rc;
-    const void *ptrs[8] = {out->edge, out->dist, out->parent, out->count, out->length, out->goal, out->cell, seen};
-    const char *names[8] = {"edge", "dist", "parent", "count", "length", "goal", "cell", "seen"};
-    for (int i = 0; i < 8; ++i)
-        if (reinterpret_cast<uintptr_t>(ptrs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_frontier: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    for (int i = 0; i < 8; ++i)
-        if (const int rc = check_device(LIB, ctx, ptrs[i], names[i])) return rc;
+    const Pointer ptrs[] = {{out->edge, "edge", 4}, {out->dist, "dist", 4}, {out->parent, "parent", 4}, {out->count, "count", 4}, {out->length, "length", 4},
+                            {out->goal, "goal", 4}, {out->cell, "cell", 4}, {seen, "seen", 4}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 8, &d_dc)) return rc;
     hipLaunchKernelGGL(frontier_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, seen, mask, *out, *spec);
     return launched(LIB);

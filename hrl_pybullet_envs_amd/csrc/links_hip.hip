@@ -109,18 +109,10 @@ int hrl_links(const hrl_config *cfg, const hrl_buffers *b, const hrl_links_spec 
     if (why.empty()) why = validate_out(out, spec);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_links: " + why);
     if (const int rc = check_record(LIB, b, "hrl_links: null state or aux")) return rc;
-    constexpr int N_OUT = 7;
-    const void *outs[N_OUT] = {out->origin, out->com, out->quat, out->lin_vel, out->ang_vel, out->site_pos, out->site_vel};
-    const char *names[N_OUT] = {"origin", "com", "quat", "lin_vel", "ang_vel", "site_pos", "site_vel"};
-    for (int i = 0; i < N_OUT; ++i)
-        if (reinterpret_cast<uintptr_t>(outs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_links: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    for (int i = 0; i < N_OUT; ++i)
-        if (const int rc = check_device(LIB, ctx, outs[i], names[i])) return rc;
+    const Pointer ptrs[] = {{out->origin, "origin", 4},   {out->com, "com", 4},           {out->quat, "quat", 4},         {out->lin_vel, "lin_vel", 4},
+                            {out->ang_vel, "ang_vel", 4}, {out->site_pos, "site_pos", 4}, {out->site_vel, "site_vel", 4}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 7, &d_dc)) return rc;
     const int groups = (cfg->num_envs + GROUP - 1) / GROUP;
     hipLaunchKernelGGL(links_kernel, dim3(groups), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, mask, *out, *spec, (int)cfg->num_envs);
     return launched(LIB);

@@ -98,18 +98,10 @@ int hrl_probe(const hrl_config *cfg, const hrl_buffers *b, const hrl_probe_spec 
     if (const int rc = check_record(LIB, b, "hrl_probe: null state or aux")) return rc;
     if (!points) return fail(HRL_ERR_BAD_ARG, "hrl_probe: null points");
     if (reinterpret_cast<uintptr_t>(points) % 8 != 0) return fail(HRL_ERR_BAD_ARG, "hrl_probe: points must be 8-byte aligned");
-    const void *outs[6] = {out->clearance, out->nearest, out->sight, out->blocker, out->path, out->via};
-    const char *names[6] = {"clearance", "nearest", "sight", "blocker", "path", "via"};
-    for (int i = 0; i < 6; ++i)
-        if (reinterpret_cast<uintptr_t>(outs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_probe: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    if (const int rc = check_device(LIB, ctx, points, "points")) return rc;
-    for (int i = 0; i < 6; ++i)
-        if (const int rc = check_device(LIB, ctx, outs[i], names[i])) return rc;
+    const Pointer ptrs[] = {{points, "points", 0},       {out->clearance, "clearance", 4}, {out->nearest, "nearest", 4}, {out->sight, "sight", 4},
+                            {out->blocker, "blocker", 4}, {out->path, "path", 4},           {out->via, "via", 4}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 7, &d_dc)) return rc;
     const int waves = (spec->n_points + 63) / 64; /* 64 points do not carry three idle waves */
     const int block = 64 * (waves < 4 ? waves : 4);
     hipLaunchKernelGGL(probe_kernel, dim3(cfg->num_envs), dim3(block), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,

@@ -86,12 +86,9 @@ int hrl_render(const hrl_config *cfg, const hrl_buffers *b, const hrl_view *view
     if (const int rc = check_record(LIB, b, NULLS)) return rc;
     if (!rgb) return fail(HRL_ERR_BAD_ARG, NULLS);
     if (reinterpret_cast<uintptr_t>(rgb) % 16 != 0) return fail(HRL_ERR_BAD_ARG, "hrl_render: rgb must be 16-byte aligned (a strip of 16 pixels is stored as three 16-byte vectors)");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    if (const int rc = check_device(LIB, ctx, rgb, "rgb")) return rc;
+    const Pointer ptrs[] = {{rgb, "rgb", 0}}; /* its alignment has the wording above */
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 1, &d_dc)) return rc;
     hipLaunchKernelGGL(render_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, mask, rgb, *view);
     return launched(LIB);

@@ -165,17 +165,9 @@ int hrl_route(const hrl_config *cfg, const hrl_buffers *b, const hrl_route_spec 
     if (why.empty()) why = validate_out(out);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_route: " + why);
     if (const int rc = check_record(LIB, b, "hrl_route: null state or aux")) return rc;
-    const void *ptrs[5] = {out->waypoints, out->count, out->length, out->cells, starts};
-    const char *names[5] = {"waypoints", "count", "length", "cells", "starts"};
-    for (int i = 0; i < 5; ++i)
-        if (reinterpret_cast<uintptr_t>(ptrs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_route: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    for (int i = 0; i < 5; ++i)
-        if (const int rc = check_device(LIB, ctx, ptrs[i], names[i])) return rc;
+    const Pointer ptrs[] = {{out->waypoints, "waypoints", 4}, {out->count, "count", 4}, {out->length, "length", 4}, {out->cells, "cells", 4}, {starts, "starts", 4}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 5, &d_dc)) return rc;
     hipLaunchKernelGGL(route_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, starts, mask, *out, *spec);
     return launched(LIB);

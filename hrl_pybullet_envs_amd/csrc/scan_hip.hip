@@ -78,13 +78,9 @@ int hrl_scan(const hrl_config *cfg, const hrl_buffers *b, const hrl_scan_spec *s
     if (const int rc = check_record(LIB, b, NULLS)) return rc;
     if (!range || !hit) return fail(HRL_ERR_BAD_ARG, NULLS);
     if (reinterpret_cast<uintptr_t>(range) % 4 != 0 || reinterpret_cast<uintptr_t>(hit) % 4 != 0) return fail(HRL_ERR_BAD_ARG, "hrl_scan: range and hit must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    if (const int rc = check_device(LIB, ctx, range, "range")) return rc;
-    if (const int rc = check_device(LIB, ctx, hit, "hit")) return rc;
+    const Pointer ptrs[] = {{range, "range", 0}, {hit, "hit", 0}}; /* their alignment has the wording above */
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 2, &d_dc)) return rc;
     const int waves = (spec->n_rays + 63) / 64; /* a 64-ray scan does not carry three idle waves */
     const int block = 64 * (waves < 4 ? waves : 4);
     hipLaunchKernelGGL(scan_kernel, dim3(cfg->num_envs), dim3(block), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,

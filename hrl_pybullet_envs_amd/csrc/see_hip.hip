@@ -100,18 +100,9 @@ int hrl_see(const hrl_config *cfg, const hrl_buffers *b, const hrl_see_spec *spe
     if (why.empty()) why = validate_out(out, spec);
     if (!why.empty()) return fail(HRL_ERR_BAD_ARG, "hrl_see: " + why);
     if (const int rc = check_record(LIB, b, "hrl_see: null state or aux")) return rc;
-    const void *outs[3] = {out->visible, out->seen, out->fresh};
-    const char *names[3] = {"visible", "seen", "fresh"};
-    for (int i = 0; i < 3; ++i)
-        if (reinterpret_cast<uintptr_t>(outs[i]) % 4 != 0) return fail(HRL_ERR_BAD_ARG, std::string("hrl_see: ") + names[i] + " must be 4-byte aligned");
-    Context ctx;
-    if (const int rc = device_context(LIB, stream, &ctx)) return rc;
-    if (const int rc = check_device(LIB, ctx, b->state, "state")) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (const int rc = check_device(LIB, ctx, outs[i], names[i])) return rc;
-    if (const int rc = check_device(LIB, ctx, clear, "clear")) return rc;
+    const Pointer ptrs[] = {{out->visible, "visible", 4}, {out->seen, "seen", 4}, {out->fresh, "fresh", 4}, {clear, "clear", 0}};
     DevCfg *d_dc = nullptr;
-    if (const int rc = devcfg_for(LIB, cfg, ctx.device, &d_dc)) return rc;
+    if (const int rc = prepare(LIB, cfg, b, stream, ptrs, 4, &d_dc)) return rc;
     hipLaunchKernelGGL(see_kernel, dim3(cfg->num_envs), dim3(BLOCK), 0, (hipStream_t)stream, (const DevCfg *)d_dc, (const float *)b->state, (const float *)b->items,
                        (const int32_t *)b->aux, clear, mask, *out, *spec);
     return launched(LIB);

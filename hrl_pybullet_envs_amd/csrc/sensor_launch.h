@@ -1,7 +1,8 @@
 /*
- * sensor_launch.h -- the host side that the sensor libraries share (render_hip.hip, scan_hip.hip, probe_hip.hip, field_hip.hip, route_hip.hip): the error
- * string, the guards of the buffer record and of the pointers' devices, the cache of kernel constants and the launch epilogue.  Host only;
- * `lib` is the library's name as its messages carry it ("hrl_scan").
+ * sensor_launch.h -- the host side that the nine sensor libraries share (render_hip.hip, scan_hip.hip, probe_hip.hip, field_hip.hip,
+ * route_hip.hip, see_hip.hip, frontier_hip.hip, camera_hip.hip, links_hip.hip): the error string, the guards of the buffer record and of the
+ * pointers' alignment and devices, the cache of kernel constants, the prologue of a launch (prepare) and its epilogue (launched).  Host
+ * only; `lib` is the library's name as its messages carry it ("hrl_scan").
  *
  * Everything here has INTERNAL linkage (one unnamed namespace, no inline or template statics): the libraries are loaded into one
  * process, and the dynamic loader may unify a symbol of vague linkage across them -- hrl_scan_last_error() would answer with the
@@ -94,6 +95,23 @@ int check_device(const char *lib, const Context &ctx, const void *p, const char 
         return fail(HRL_ERR_BAD_ARG, std::string(lib) + ": " + name + " lives on HIP device " + std::to_string(a.device) + ", the current device is " + std::to_string(ctx.device) +
                                          ": hipSetDevice(" + std::to_string(a.device) + ") before calling");
     return HRL_OK;
+}
+
+/* A pointer a launch is handed, as the messages name it; `align`: the bytes its address must be a multiple of, 0 = not checked here. */
+struct Pointer { const void *p; const char *name; unsigned align; };
+
+/* What the entry points of the record-style sensors do between check_record and the launch, in this order: the alignment of `ptrs` in
+ * list order (a null pointer is aligned), the context, the device of `state` and of `ptrs` in list order, the kernel constants. */
+int prepare(const char *lib, const hrl_config *cfg, const hrl_buffers *b, void *stream, const Pointer *ptrs, int n, hrl::DevCfg **d_dc) {
+    for (int i = 0; i < n; ++i)
+        if (ptrs[i].align && reinterpret_cast<uintptr_t>(ptrs[i].p) % ptrs[i].align != 0)
+            return fail(HRL_ERR_BAD_ARG, std::string(lib) + ": " + ptrs[i].name + " must be " + std::to_string(ptrs[i].align) + "-byte aligned");
+    Context ctx;
+    if (const int rc = device_context(lib, stream, &ctx)) return rc;
+    if (const int rc = check_device(lib, ctx, b->state, "state")) return rc;
+    for (int i = 0; i < n; ++i)
+        if (const int rc = check_device(lib, ctx, ptrs[i].p, ptrs[i].name)) return rc;
+    return devcfg_for(lib, cfg, ctx.device, d_dc);
 }
 
 /* after hipLaunchKernelGGL */

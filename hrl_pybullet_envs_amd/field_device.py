@@ -5,7 +5,6 @@ one kernel launch.  The grid is the renderer's pixel grid: a field and an image 
 
 Like the renderer's, the scanner's and the probes', the library is the step library's neighbour, not a part of it.  There is no CPU
 fallback: a missing library is an error."""
-import collections
 import ctypes as C
 import os
 
@@ -23,9 +22,8 @@ SOURCE, UNREACHED, BLOCKED = 8, 9, 10        # `parent` beyond the direction cod
 DIRECTIONS = ((1, 0), (1, -1), (0, -1), (-1, -1), (-1, 0), (-1, 1), (0, 1), (1, 1))   # (dcol, drow) of code 0..7 = E, NE, N, NW, W, SW, S, SE; row - 1 is N
 SQRT2 = 1.41421354
 
-Field = collections.namedtuple('Field', 'dist parent')
-Field.__new__.__defaults__ = (None,) * 2
 FIELDS = (('dist', torch.float32), ('parent', torch.uint8))
+Field, hrl_field_out = _sensor.out_types('Field', 'hrl_field_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_FIELD_LIB') or os.path.join(_PKG, 'libhrl_field_hip.so')
@@ -35,10 +33,6 @@ SYMBOLS = ['hrl_field_default_spec', 'hrl_field', 'hrl_field_last_error']   # ev
 class hrl_field_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('mode', C.c_int32), ('centre', C.c_float * 2),
                 ('half_extent', C.c_float), ('blocking', C.c_uint32), ('sources', C.c_uint32), ('margin', C.c_float)]
-
-
-class hrl_field_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_field', 'the batched navigation field has', {
@@ -109,14 +103,23 @@ def cell_index(spec, state, xy):
 def field(cfg, bufs_ref, spec, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Field; a None one is not computed), each [N, height, width] on the current device, from the
     buffer record behind `bufs_ref`."""
-    o = _sensor.out_record(hrl_field_out, FIELDS, out)
-    check(lib().hrl_field(C.byref(cfg), bufs_ref, C.byref(spec), mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_field, hrl_field_out, FIELDS, cfg, bufs_ref, spec, (mask_ptr,), out, stream)
+
+
+def shapes(spec, lead=()):
+    """The shape after N of each member of Field (with `lead` = (N,): the whole shape)."""
+    return (lead + (spec.height, spec.width),) * 2
+
+
+def size_error(spec):
+    """Why no tensors can be shaped after the spec's grid (the library refuses it too), or None.  The grids of see_device and
+    frontier_device are this one."""
+    if MIN_SIZE <= spec.width <= MAX_SIZE and MIN_SIZE <= spec.height <= MAX_SIZE:
+        return None
+    return f'spec.width and spec.height must be within {MIN_SIZE}..{MAX_SIZE}, got {spec.width} x {spec.height}'
 
 
 def check_out(out, n, spec, device):
     """`out=` of BatchedEnv.field(): a Field whose members are None (skipped) or contiguous, 4-byte aligned [N, height, width] tensors of the
     member's dtype on the env's device; at least one must be given."""
-    if not isinstance(out, Field):
-        raise TypeError('out must be a field_device.Field (a None member is skipped)')
-    return _sensor.check_tensors(out, 'out.', FIELDS, (n, spec.height, spec.width), device, 4, optional=True)
+    return _sensor.check_out(Field, 'field_device', FIELDS, shapes(spec, (n,)), out, device)

@@ -7,7 +7,6 @@ index), in HBM, from one kernel launch.
 
 Like the other sensors', the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a missing library is
 an error."""
-import collections
 import ctypes as C
 import os
 
@@ -15,17 +14,16 @@ import torch
 
 from . import _capi as K
 from . import _sensor
-from .field_device import BLOCKED, DIRECTIONS, MAX_MARGIN, MAX_SIZE, MIN_SIZE, ROBOT, SOURCE, UNREACHED, cell_size  # noqa: F401  (the field's grid and codes)
+from .field_device import BLOCKED, DIRECTIONS, MAX_MARGIN, MAX_SIZE, MIN_SIZE, ROBOT, SOURCE, UNREACHED, cell_size, size_error  # noqa: F401  (the field's grid and codes)
 from .scan_device import ALL, BOX, FOOD, POISON, TARGET, WALL  # noqa: F401  (the scanner's class bits)
 
 EDGE = 64                                    # HRL_FRONTIER_EDGE: a source bit next to ROBOT | FOOD | POISON | TARGET
 KNOWN_ONLY, OPTIMISTIC = 0, 1                # hrl_frontier_spec.unknown
 UNKNOWN = {'known': KNOWN_ONLY, 'optimistic': OPTIMISTIC}
 
-Frontier = collections.namedtuple('Frontier', 'edge dist parent count length goal cell')
-Frontier.__new__.__defaults__ = (None,) * 7
 FIELDS = (('edge', torch.uint8), ('dist', torch.float32), ('parent', torch.uint8), ('count', torch.int32), ('length', torch.float32), ('goal', torch.float32),
           ('cell', torch.int32))
+Frontier, hrl_frontier_out = _sensor.out_types('Frontier', 'hrl_frontier_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_FRONTIER_LIB') or os.path.join(_PKG, 'libhrl_frontier_hip.so')
@@ -35,10 +33,6 @@ SYMBOLS = ['hrl_frontier_default_spec', 'hrl_frontier', 'hrl_frontier_last_error
 class hrl_frontier_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('centre', C.c_float * 2), ('half_extent', C.c_float),
                 ('blocking', C.c_uint32), ('sources', C.c_uint32), ('margin', C.c_float), ('unknown', C.c_int32)]
-
-
-class hrl_frontier_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_frontier', 'the batched frontier map has', {
@@ -81,24 +75,22 @@ def spec_like(cfg, see_spec, sources=EDGE, unknown='known', margin=None):
     return s
 
 
-def shapes(spec):
-    """The shape after N of each member of Frontier."""
-    grid = (spec.height, spec.width)
-    return (grid, grid, grid, (), (), (2,), ())
+def shapes(spec, lead=()):
+    """The shape after N of each member of Frontier (with `lead` = (N,): the whole shape)."""
+    grid = lead + (spec.height, spec.width)
+    return (grid, grid, grid, lead, lead, lead + (2,), lead)
 
 
 def frontier(cfg, bufs_ref, spec, seen_ptr, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Frontier; a None one is not computed) on the current device, from the buffer record behind
     `bufs_ref` and the memory at `seen_ptr`, which is only read."""
-    o = _sensor.out_record(hrl_frontier_out, FIELDS, out)
-    check(lib().hrl_frontier(C.byref(cfg), bufs_ref, C.byref(spec), seen_ptr, mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_frontier, hrl_frontier_out, FIELDS, cfg, bufs_ref, spec, (seen_ptr, mask_ptr), out, stream)
 
 
 def check_seen(seen, n, spec, device):
     """`seen` of BatchedEnv.frontier(): the memory of BatchedEnv.see() on the same grid -- a contiguous, 4-byte aligned uint8 [N, height,
     width] tensor on the env's device."""
-    _sensor.check_tensors((seen,), '', (('seen', torch.uint8),), (n, spec.height, spec.width), device, 4)
+    _sensor.check_tensors((seen,), '', (('seen', torch.uint8),), ((n, spec.height, spec.width),), device, 4)
     return seen
 
 
@@ -106,15 +98,7 @@ def check_out(out, n, spec, device, seen=None):
     """`out=` of BatchedEnv.frontier(): a Frontier whose members are None (skipped) or contiguous, 4-byte aligned tensors of the member's
     dtype -- edge, dist and parent [N, height, width], count, length and cell [N], goal [N, 2] -- on the env's device; at least one must
     be given.  `edge` and `parent` must not be the memory of `seen` (the library refuses that too)."""
-    if not isinstance(out, Frontier):
-        raise TypeError('out must be a frontier_device.Frontier (a None member is skipped)')
-    none = True
-    for field, shape, t in zip(FIELDS, shapes(spec), out):
-        if t is not None:
-            none = False
-            _sensor.check_tensors((t,), 'out.', (field,), (n,) + shape, device, 4)
-    if none:
-        raise ValueError('out holds no tensor: at least one output must be given')
+    _sensor.check_out(Frontier, 'frontier_device', FIELDS, shapes(spec, (n,)), out, device)
     if seen is not None:
         for name in ('edge', 'parent'):
             t = getattr(out, name)

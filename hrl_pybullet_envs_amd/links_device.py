@@ -6,7 +6,6 @@ the reference reads one env at a time through `robot.parts[name]` and the simula
 
 Like the other sensors', the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a missing library is
 an error."""
-import collections
 import ctypes as C
 import os
 
@@ -24,9 +23,8 @@ FEET = (2, 4, 6, 8)     # HRL_LINK_FOOT(l): upstream's foot_list order
 HIPS = (9, 10, 11, 12)  # HRL_LINK_HIP(l)
 FOOT_LIST = ('front_left_foot', 'front_right_foot', 'left_back_foot', 'right_back_foot')   # upstream Ant.foot_list
 
-Links = collections.namedtuple('Links', 'origin com quat lin_vel ang_vel site_pos site_vel')
-Links.__new__.__defaults__ = (None,) * 7
-FIELDS = tuple((name, torch.float32) for name in Links._fields)
+FIELDS = tuple((name, torch.float32) for name in ('origin', 'com', 'quat', 'lin_vel', 'ang_vel', 'site_pos', 'site_vel'))
+Links, hrl_links_out = _sensor.out_types('Links', 'hrl_links_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_LINKS_LIB') or os.path.join(_PKG, 'libhrl_links_hip.so')
@@ -35,10 +33,6 @@ SYMBOLS = ['hrl_links_count', 'hrl_links_name', 'hrl_links_default_spec', 'hrl_l
 
 class hrl_links_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('frame', C.c_int32), ('n_sites', C.c_int32), ('site_link', C.c_int32 * MAX_SITES), ('site_local', (C.c_float * 3) * MAX_SITES)]
-
-
-class hrl_links_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_links', 'the batched link states have', {
@@ -90,40 +84,30 @@ def tip(links):
     return 2 * links.com - links.origin
 
 
-def shapes(cfg, spec):
-    """The shape after N of each member of Links."""
-    b, s = n_links(cfg), spec.n_sites
-    return ((b, 3), (b, 3), (b, 4), (b, 3), (b, 3), (s, 3), (s, 3))
+def shapes(cfg, spec, lead=()):
+    """The shape after N of each member of Links (with `lead` = (N,): the whole shape)."""
+    link, site = lead + (n_links(cfg), 3), lead + (spec.n_sites, 3)
+    return (link, link, link[:-1] + (4,), link, link, site, site)
+
+
+def size_error(spec):
+    """Why no tensors can be shaped after the spec (the library refuses it too), or None."""
+    return None if 0 <= spec.n_sites <= MAX_SITES else f'spec.n_sites must be within 0..{MAX_SITES}, got {spec.n_sites}'
 
 
 def sized(spec):
-    """Whether tensors can be shaped after the spec (the library refuses the others too)."""
-    return 0 <= spec.n_sites <= MAX_SITES
+    """Whether tensors can be shaped after the spec."""
+    return size_error(spec) is None
 
 
 def links(cfg, bufs_ref, spec, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Links; a None one is not computed) on the current device, from the buffer record behind
     `bufs_ref`."""
-    o = _sensor.out_record(hrl_links_out, FIELDS, out)
-    check(lib().hrl_links(C.byref(cfg), bufs_ref, C.byref(spec), mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_links, hrl_links_out, FIELDS, cfg, bufs_ref, spec, (mask_ptr,), out, stream)
 
 
 def check_out(out, n, cfg, spec, device):
     """`out=` of BatchedEnv.links(): a Links whose members are None (skipped) or contiguous, 4-byte aligned float32 tensors -- origin, com,
     lin_vel, ang_vel [N, B, 3], quat [N, B, 4], site_pos, site_vel [N, n_sites, 3] -- on the env's device, no two of them the same memory;
     at least one must be given."""
-    if not isinstance(out, Links):
-        raise TypeError('out must be a links_device.Links (a None member is skipped)')
-    given = []
-    for field, shape, t in zip(FIELDS, shapes(cfg, spec), out):
-        if t is not None:
-            _sensor.check_tensors((t,), 'out.', (field,), (n,) + shape, device, 4)
-            given.append((field[0], t))
-    if not given:
-        raise ValueError('out holds no tensor: at least one output must be given')
-    for k, (a, x) in enumerate(given):
-        for b, y in given[k + 1:]:
-            if x.data_ptr() == y.data_ptr() and x.numel() and y.numel():
-                raise ValueError(f'out.{a} and out.{b} must not be the same memory')
-    return out
+    return _sensor.check_out(Links, 'links_device', FIELDS, shapes(cfg, spec, (n,)), out, device, distinct=True)

@@ -4,7 +4,6 @@ blocker and path / via, each [N, P] in HBM, from one kernel launch.
 
 Like the renderer's and the scanner's, the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a
 missing library is an error."""
-import collections
 import ctypes as C
 import os
 
@@ -21,9 +20,8 @@ MAX_MARGIN = 2.0
 SKIN = 1e-3
 VIA_NONE, VIA_STRAIGHT, VIA_CORNER0 = 0, 1, 2                                    # `via`: 2 + k = the route first turns at corner k
 
-Probe = collections.namedtuple('Probe', 'clearance nearest sight blocker path via')
-Probe.__new__.__defaults__ = (None,) * 6
 FIELDS = (('clearance', torch.float32), ('nearest', torch.int32), ('sight', torch.float32), ('blocker', torch.int32), ('path', torch.float32), ('via', torch.int32))
+Probe, hrl_probe_out = _sensor.out_types('Probe', 'hrl_probe_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_PROBE_LIB') or os.path.join(_PKG, 'libhrl_probe_hip.so')
@@ -32,10 +30,6 @@ SYMBOLS = ['hrl_probe_default_spec', 'hrl_probe', 'hrl_probe_last_error']   # ev
 
 class hrl_probe_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('n_points', C.c_int32), ('frame', C.c_int32), ('classes', C.c_uint32), ('margin', C.c_float)]
-
-
-class hrl_probe_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_probe', 'the batched point probes have', {
@@ -76,25 +70,25 @@ def corner_table(cfg, margin):
 def probe(cfg, bufs_ref, spec, points, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Probe; None fields are not computed), each [N, n_points] on the current device, from the
     buffer record behind `bufs_ref` and `points` float32 [N, n_points, 2]."""
-    o = _sensor.out_record(hrl_probe_out, FIELDS, out)
-    check(lib().hrl_probe(C.byref(cfg), bufs_ref, C.byref(spec), points.data_ptr(), mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_probe, hrl_probe_out, FIELDS, cfg, bufs_ref, spec, (points.data_ptr(), mask_ptr), out, stream)
+
+
+def shapes(spec, lead=()):
+    """The shape after N of each member of Probe (with `lead` = (N,): the whole shape)."""
+    return (lead + (spec.n_points,),) * 6
+
+
+def size_error(spec):
+    """Why no tensors can be shaped after the spec (the library refuses it too), or None."""
+    return None if 1 <= spec.n_points <= MAX_POINTS else f'spec.n_points must be within 1..{MAX_POINTS}, got {spec.n_points}'
 
 
 def check_points(points, n, device):
     """`points` of BatchedEnv.probe(): float32, contiguous [N, P, 2] with 1 <= P <= 512, on the env's device."""
-    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32:
-        raise TypeError(f'points must be a torch.float32 tensor, got {getattr(points, "dtype", type(points))}')
-    if points.dim() != 3 or points.shape[0] != n or points.shape[2] != 2 or not 1 <= points.shape[1] <= MAX_POINTS or not points.is_contiguous():
-        raise ValueError(f'points must be contiguous [{n}, P, 2] with 1 <= P <= {MAX_POINTS}, got {tuple(points.shape)}')
-    if points.device != device:
-        raise ValueError(f'points live on {points.device}, the env on {device}')
-    return points
+    return _sensor.check_points(points, 'points', MAX_POINTS, n, device)
 
 
 def check_out(out, n, spec, device):
     """`out=` of BatchedEnv.probe(): a Probe whose fields are None (skipped) or contiguous, 4-byte aligned [N, n_points] tensors of the field's dtype
     on the env's device; at least one must be given."""
-    if not isinstance(out, Probe):
-        raise TypeError('out must be a probe_device.Probe (None fields are skipped)')
-    return _sensor.check_tensors(out, 'out.', FIELDS, (n, spec.n_points), device, 4, optional=True)
+    return _sensor.check_out(Probe, 'probe_device', FIELDS, shapes(spec, (n,)), out, device, note='None fields are skipped')

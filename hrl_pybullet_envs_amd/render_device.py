@@ -61,4 +61,4 @@ def render(cfg, bufs_ref, view, mask_ptr, out, stream):
 
 def check_out(out, n, view, device):
     """`out=` of BatchedEnv.render(): uint8 [N, H, W, 3], contiguous, 16-byte aligned, on the env's device."""
-    return _sensor.check_tensors((out,), 'out', (('', torch.uint8),), (n, view.height, view.width, 3), device, 16)[0]
+    return _sensor.check_tensors((out,), 'out', (('', torch.uint8),), ((n, view.height, view.width, 3),), device, 16)[0]

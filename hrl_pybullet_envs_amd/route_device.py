@@ -5,7 +5,6 @@ field, pulled tight into at most K waypoints: `waypoints` float32 [N, P, K, 2] (
 
 Like the other sensors', the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a missing library is
 an error."""
-import collections
 import ctypes as C
 import os
 
@@ -20,9 +19,8 @@ from .render_device import HRL_VIEW_EGO, HRL_VIEW_EGO_HEADING, HRL_VIEW_WORLD, M
 MAX_STARTS = 64
 MIN_WAYPOINTS, MAX_WAYPOINTS = 2, 32
 
-Route = collections.namedtuple('Route', 'waypoints count length cells')
-Route.__new__.__defaults__ = (None,) * 4
 FIELDS = (('waypoints', torch.float32), ('count', torch.int32), ('length', torch.float32), ('cells', torch.int32))
+Route, hrl_route_out = _sensor.out_types('Route', 'hrl_route_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_ROUTE_LIB') or os.path.join(_PKG, 'libhrl_route_hip.so')
@@ -33,10 +31,6 @@ class hrl_route_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('mode', C.c_int32), ('centre', C.c_float * 2),
                 ('half_extent', C.c_float), ('blocking', C.c_uint32), ('sources', C.c_uint32), ('margin', C.c_float),
                 ('n_starts', C.c_int32), ('frame', C.c_int32), ('max_waypoints', C.c_int32)]
-
-
-class hrl_route_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_route', 'the batched routes have', {
@@ -70,41 +64,32 @@ def from_field_spec(fspec, frame='ego', n_starts=1, max_waypoints=16):
                           sources=fspec.sources, margin=fspec.margin, n_starts=int(n_starts), frame=_frame(frame), max_waypoints=int(max_waypoints))
 
 
-def shapes(spec):
-    """The shape after N of each member of Route."""
-    p, k = spec.n_starts, spec.max_waypoints
-    return ((p, k, 2), (p,), (p,), (p, k))
+def shapes(spec, lead=()):
+    """The shape after N of each member of Route (with `lead` = (N,): the whole shape)."""
+    starts = lead + (spec.n_starts,)
+    kept = starts + (spec.max_waypoints,)
+    return (kept + (2,), starts, starts, kept)
+
+
+def size_error(spec):
+    """Why no tensors can be shaped after the spec (the library refuses it too), or None."""
+    if MIN_WAYPOINTS <= spec.max_waypoints <= MAX_WAYPOINTS:
+        return None
+    return f'spec.max_waypoints must be within {MIN_WAYPOINTS}..{MAX_WAYPOINTS}, got {spec.max_waypoints}'
 
 
 def route(cfg, bufs_ref, spec, starts, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a Route; a None one is not computed) on the current device, from the buffer record behind
     `bufs_ref` and `starts` float32 [N, n_starts, 2] (None: the robot's place)."""
-    o = _sensor.out_record(hrl_route_out, FIELDS, out)
-    check(lib().hrl_route(C.byref(cfg), bufs_ref, C.byref(spec), None if starts is None else starts.data_ptr(), mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_route, hrl_route_out, FIELDS, cfg, bufs_ref, spec, (None if starts is None else starts.data_ptr(), mask_ptr), out, stream)
 
 
 def check_starts(starts, n, device):
     """`starts` of BatchedEnv.route(): float32, contiguous [N, P, 2] with 1 <= P <= 64, on the env's device."""
-    if not isinstance(starts, torch.Tensor) or starts.dtype != torch.float32:
-        raise TypeError(f'starts must be a torch.float32 tensor, got {getattr(starts, "dtype", type(starts))}')
-    if starts.dim() != 3 or starts.shape[0] != n or starts.shape[2] != 2 or not 1 <= starts.shape[1] <= MAX_STARTS or not starts.is_contiguous():
-        raise ValueError(f'starts must be contiguous [{n}, P, 2] with 1 <= P <= {MAX_STARTS}, got {tuple(starts.shape)}')
-    if starts.device != device:
-        raise ValueError(f'starts live on {starts.device}, the env on {device}')
-    return starts
+    return _sensor.check_points(starts, 'starts', MAX_STARTS, n, device)
 
 
 def check_out(out, n, spec, device):
     """`out=` of BatchedEnv.route(): a Route whose members are None (skipped) or contiguous, 4-byte aligned tensors of the member's dtype
     and shape (shapes(spec) after N) on the env's device; at least one must be given."""
-    if not isinstance(out, Route):
-        raise TypeError('out must be a route_device.Route (a None member is skipped)')
-    none = True
-    for field, shape, t in zip(FIELDS, shapes(spec), out):
-        if t is not None:
-            none = False
-            _sensor.check_tensors((t,), 'out.', (field,), (n,) + shape, device, 4)
-    if none:
-        raise ValueError('out holds no tensor: at least one output must be given')
-    return out
+    return _sensor.check_out(Route, 'route_device', FIELDS, shapes(spec, (n,)), out, device)

@@ -71,6 +71,11 @@ def decode(hit):
     return hit & 0xFF, hit >> 8
 
 
+def size_error(spec):
+    """Why no tensors can be shaped after the spec (the library refuses it too), or None."""
+    return None if 1 <= spec.n_rays <= MAX_RAYS else f'spec.n_rays must be within 1..{MAX_RAYS}, got {spec.n_rays}'
+
+
 def scan(cfg, bufs_ref, spec, mask_ptr, rng, hit, stream):
     """One launch: `rng` float32 and `hit` int32, [N, n_rays] on the current device, from the buffer record behind `bufs_ref`."""
     check(lib().hrl_scan(C.byref(cfg), bufs_ref, C.byref(spec), mask_ptr, rng.data_ptr(), hit.data_ptr(), stream))
@@ -81,5 +86,5 @@ def check_out(out, n, spec, device):
     """`out=` of BatchedEnv.scan(): (range float32, hit int32), each contiguous [N, n_rays], 4-byte aligned, on the env's device."""
     if not isinstance(out, (tuple, list)) or len(out) != 2:
         raise TypeError('out must be a pair (range, hit)')
-    _sensor.check_tensors(out, 'out ', FIELDS, (n, spec.n_rays), device, 4)
+    _sensor.check_tensors(out, 'out ', FIELDS, ((n, spec.n_rays),) * 2, device, 4)
     return out[0], out[1]

@@ -5,7 +5,6 @@ and written) and how many it saw for the first time (`fresh` int32 [N]), in HBM,
 
 Like the other sensors', the library is the step library's neighbour, not a part of it.  There is no CPU fallback: a missing library is
 an error."""
-import collections
 import ctypes as C
 import math
 import os
@@ -14,15 +13,14 @@ import torch
 
 from . import _capi as K
 from . import _sensor
-from .field_device import MAX_SIZE, MIN_SIZE, cell_size  # noqa: F401  (the field's grid)
+from .field_device import MAX_SIZE, MIN_SIZE, cell_size, size_error  # noqa: F401  (the field's grid)
 from .render_device import HRL_VIEW_EGO, HRL_VIEW_EGO_HEADING, HRL_VIEW_WORLD, MODES, _mode  # noqa: F401  (the renderer's modes)
 from .scan_device import ALL, BOX, FOOD, POISON, TARGET, WALL  # noqa: F401  (the scanner's class bits)
 
 MAX_SLACK = 2.0   # HRL_PROBE_MAX_MARGIN
 
-See = collections.namedtuple('See', 'visible seen fresh')
-See.__new__.__defaults__ = (None,) * 3
 FIELDS = (('visible', torch.uint8), ('seen', torch.uint8), ('fresh', torch.int32))
+See, hrl_see_out = _sensor.out_types('See', 'hrl_see_out', FIELDS, __name__)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HRL_SEE_LIB') or os.path.join(_PKG, 'libhrl_see_hip.so')
@@ -32,10 +30,6 @@ SYMBOLS = ['hrl_see_default_spec', 'hrl_see', 'hrl_see_last_error']   # every sy
 class hrl_see_spec(_sensor.Spec):
     _fields_ = [('struct_size', C.c_uint64), ('width', C.c_int32), ('height', C.c_int32), ('mode', C.c_int32), ('centre', C.c_float * 2),
                 ('half_extent', C.c_float), ('occluders', C.c_uint32), ('max_range', C.c_float), ('fov_cos', C.c_float), ('slack', C.c_float)]
-
-
-class hrl_see_out(C.Structure):
-    _fields_ = [(name, C.c_void_p) for name, _ in FIELDS]
 
 
 lib, check = _sensor.loader(lambda: LIB_PATH, SYMBOLS, 'hrl_see', 'the batched visibility map has', {
@@ -72,32 +66,23 @@ def memory(n, spec, device):
     return torch.zeros(n, spec.height, spec.width, dtype=torch.uint8, device=device)
 
 
-def shapes(spec):
-    """The shape after N of each member of See."""
-    return ((spec.height, spec.width), (spec.height, spec.width), ())
+def shapes(spec, lead=()):
+    """The shape after N of each member of See (with `lead` = (N,): the whole shape)."""
+    grid = lead + (spec.height, spec.width)
+    return (grid, grid, lead)
 
 
 def see(cfg, bufs_ref, spec, clear_ptr, mask_ptr, out, stream):
     """One launch: the tensors of `out` (a See; a None one is not computed; `seen` is read and written) on the current device, from the
     buffer record behind `bufs_ref`."""
-    o = _sensor.out_record(hrl_see_out, FIELDS, out)
-    check(lib().hrl_see(C.byref(cfg), bufs_ref, C.byref(spec), clear_ptr, mask_ptr, C.byref(o), stream))
-    return out
+    return _sensor.launch(check, lib().hrl_see, hrl_see_out, FIELDS, cfg, bufs_ref, spec, (clear_ptr, mask_ptr), out, stream)
 
 
 def check_out(out, n, spec, device):
     """`out=` of BatchedEnv.see(): a See whose members are None (skipped) or contiguous, 4-byte aligned tensors of the member's dtype --
     visible and seen [N, height, width], fresh [N] -- on the env's device; at least one must be given.  `seen` needs the world mode, `fresh`
     needs `seen`, and `visible` and `seen` must be different memory (the library refuses these too)."""
-    if not isinstance(out, See):
-        raise TypeError('out must be a see_device.See (a None member is skipped)')
-    none = True
-    for field, shape, t in zip(FIELDS, shapes(spec), out):
-        if t is not None:
-            none = False
-            _sensor.check_tensors((t,), 'out.', (field,), (n,) + shape, device, 4)
-    if none:
-        raise ValueError('out holds no tensor: at least one output must be given')
+    _sensor.check_out(See, 'see_device', FIELDS, shapes(spec, (n,)), out, device)
     if out.seen is not None and spec.mode != HRL_VIEW_WORLD:
         raise ValueError("out.seen needs a spec in the 'world' mode: an ego grid moves under the memory")
     if out.fresh is not None and out.seen is None:

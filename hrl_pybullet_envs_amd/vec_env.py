@@ -142,7 +142,7 @@ class BatchedEnv:
                 b.contacts = p
         return self.contacts
 
-    # the sensors (render, scan, probe, field, route, see, frontier, camera): each is one launch of a library of its own on the state / items / aux tensors as they are
+    # the sensors (render, scan, probe, field, route, see, frontier, camera, links): each is one launch of a library of its own on the state / items / aux tensors as they are
     def _default_spec(self, key, make):
         """The spec a sensor uses when none is given: asked of its library once per `key`."""
         specs = self.__dict__.setdefault('_default_specs', {})
@@ -153,6 +153,15 @@ class BatchedEnv:
     def _fresh(self, mask, shape, dtype):
         """A new output tensor [N, *shape]: zeros where a mask may leave envs unwritten."""
         return (torch.empty if mask is None else torch.zeros)(self.num_envs, *shape, dtype=dtype, device=self.device)
+
+    def _fresh_out(self, M, kind, shapes, spec, mask, only=None):
+        """The new outputs of a record-style sensor (binding M, namedtuple `kind`): a _fresh tensor per entry of `shapes` (M.shapes), of the
+        first `only` when given; None where there is nothing to write (a first entry of 0).  M.size_error(spec) is raised: no tensor can
+        be shaped after such a spec."""
+        why = M.size_error(spec)
+        if why is not None:
+            raise ValueError(why)
+        return kind(*(self._fresh(mask, shape, dtype) if shape[:1] != (0,) else None for shape, (_, dtype) in zip(shapes[:only], M.FIELDS)))
 
     def _sensor_launch(self, keep, mask, launch):
         """launch(mask pointer or None, stream) on this env's device and the current stream; the converted mask stays alive as attribute `keep`."""
@@ -191,8 +200,9 @@ class BatchedEnv:
         if spec is None:
             spec = self._default_spec('scan', lambda: S.default_spec(self.cfg))
         if out is None:
-            if not 1 <= spec.n_rays <= S.MAX_RAYS:   # (the library refuses it too; no tensor can be shaped after it)
-                raise ValueError(f'spec.n_rays must be within 1..{S.MAX_RAYS}, got {spec.n_rays}')
+            why = S.size_error(spec)
+            if why is not None:
+                raise ValueError(why)
             rng, hit = self._fresh(mask, (spec.n_rays,), torch.float32), self._fresh(mask, (spec.n_rays,), torch.int32)
         else:
             rng, hit = S.check_out(out, self.num_envs, spec, self.device)
@@ -215,10 +225,7 @@ class BatchedEnv:
             spec = self._default_spec(('probe', points.shape[1]), lambda: P.default_spec(self.cfg, 'world', points.shape[1]))
         elif spec.n_points != points.shape[1]:
             raise ValueError(f'spec.n_points is {spec.n_points}, points hold {points.shape[1]} per env')
-        if out is None:
-            out = P.Probe(*(self._fresh(mask, (spec.n_points,), dtype) for _, dtype in P.FIELDS))
-        else:
-            P.check_out(out, self.num_envs, spec, self.device)
+        out = self._fresh_out(P, P.Probe, P.shapes(spec), spec, mask) if out is None else P.check_out(out, self.num_envs, spec, self.device)
         self._sensor_launch('_last_probe_mask', mask, lambda m, stream: P.probe(self.cfg, self._bufs_ref, spec, points, m, out, stream))
         return out
 
@@ -235,12 +242,7 @@ class BatchedEnv:
         from . import field_device as F
         if spec is None:
             spec = self._default_spec('field', lambda: F.default_spec(self.cfg))
-        if out is None:
-            if not (F.MIN_SIZE <= spec.width <= F.MAX_SIZE and F.MIN_SIZE <= spec.height <= F.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
-                raise ValueError(f'spec.width and spec.height must be within {F.MIN_SIZE}..{F.MAX_SIZE}, got {spec.width} x {spec.height}')
-            out = F.Field(*(self._fresh(mask, (spec.height, spec.width), dtype) for _, dtype in F.FIELDS))
-        else:
-            F.check_out(out, self.num_envs, spec, self.device)
+        out = self._fresh_out(F, F.Field, F.shapes(spec), spec, mask) if out is None else F.check_out(out, self.num_envs, spec, self.device)
         self._sensor_launch('_last_field_mask', mask, lambda m, stream: F.field(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
@@ -263,12 +265,7 @@ class BatchedEnv:
             spec = self._default_spec(('route', p), lambda: R.default_spec(self.cfg, n_starts=p))
         elif spec.n_starts != p:
             raise ValueError(f'spec.n_starts is {spec.n_starts}, starts hold {p} per env' if starts is not None else f'spec.n_starts is {spec.n_starts}: without starts there is one per env, the robot')
-        if out is None:
-            if not R.MIN_WAYPOINTS <= spec.max_waypoints <= R.MAX_WAYPOINTS:   # (the library refuses it too; no tensor can be shaped after it)
-                raise ValueError(f'spec.max_waypoints must be within {R.MIN_WAYPOINTS}..{R.MAX_WAYPOINTS}, got {spec.max_waypoints}')
-            out = R.Route(*(self._fresh(mask, shape, dtype) for shape, (_, dtype) in zip(R.shapes(spec), R.FIELDS)))
-        else:
-            R.check_out(out, self.num_envs, spec, self.device)
+        out = self._fresh_out(R, R.Route, R.shapes(spec), spec, mask) if out is None else R.check_out(out, self.num_envs, spec, self.device)
         self._sensor_launch('_last_route_mask', mask, lambda m, stream: R.route(self.cfg, self._bufs_ref, spec, starts, m, out, stream))
         return out
 
@@ -287,13 +284,8 @@ class BatchedEnv:
         from . import see_device as V
         if spec is None:
             spec = self._default_spec('see', lambda: V.default_spec(self.cfg))
-        if out is None:
-            if not (V.MIN_SIZE <= spec.width <= V.MAX_SIZE and V.MIN_SIZE <= spec.height <= V.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
-                raise ValueError(f'spec.width and spec.height must be within {V.MIN_SIZE}..{V.MAX_SIZE}, got {spec.width} x {spec.height}')
-            out = V.See(self._fresh(mask, (spec.height, spec.width), torch.uint8), None, None)
-        else:
-            V.check_out(out, self.num_envs, spec, self.device)
-        c = None if clear is None else clear.to(device=self.device, dtype=torch.uint8).contiguous()
+        out = self._fresh_out(V, V.See, V.shapes(spec), spec, mask, only=1) if out is None else V.check_out(out, self.num_envs, spec, self.device)
+        c =None if clear is None else clear.to(device=self.device, dtype=torch.uint8).contiguous()
         if c is not None and tuple(c.shape) != (self.num_envs,):
             raise ValueError(f'clear must be [{self.num_envs}], got {tuple(c.shape)}')
         self._sensor_launch('_last_see_mask', mask, lambda m, stream: V.see(self.cfg, self._bufs_ref, spec, None if c is None else c.data_ptr(), m, out, stream))
@@ -317,13 +309,11 @@ class BatchedEnv:
         from . import frontier_device as X
         if spec is None:
             spec = self._default_spec('frontier', lambda: X.default_spec(self.cfg))
-        if not (X.MIN_SIZE <= spec.width <= X.MAX_SIZE and X.MIN_SIZE <= spec.height <= X.MAX_SIZE):   # (the library refuses it too; no tensor can be shaped after it)
-            raise ValueError(f'spec.width and spec.height must be within {X.MIN_SIZE}..{X.MAX_SIZE}, got {spec.width} x {spec.height}')
+        why = X.size_error(spec)   # before `seen` is measured against the spec, so with `out` given too
+        if why is not None:
+            raise ValueError(why)
         X.check_seen(seen, self.num_envs, spec, self.device)
-        if out is None:
-            out = X.Frontier(*(self._fresh(mask, shape, dtype) for shape, (_, dtype) in zip(X.shapes(spec), X.FIELDS)))
-        else:
-            X.check_out(out, self.num_envs, spec, self.device, seen)
+        out = self._fresh_out(X, X.Frontier, X.shapes(spec), spec, mask) if out is None else X.check_out(out, self.num_envs, spec, self.device, seen)
         self._sensor_launch('_last_frontier_mask', mask, lambda m, stream: X.frontier(self.cfg, self._bufs_ref, spec, seen.data_ptr(), m, out, stream))
         return out
 
@@ -340,12 +330,7 @@ class BatchedEnv:
         from . import camera_device as Cm
         if spec is None:
             spec = self._default_spec('camera', lambda: Cm.default_spec(self.cfg))
-        if out is None:
-            if not Cm.sized(spec):   # (the library refuses it too; no tensor can be shaped after it)
-                raise ValueError(f'spec.width must be within {Cm.MIN_WIDTH}..{Cm.MAX_SIZE} and spec.height within {Cm.MIN_HEIGHT}..{Cm.MAX_SIZE}, got {spec.width} x {spec.height}')
-            out = Cm.Camera(*(self._fresh(mask, shape, dtype) for shape, (_, dtype) in zip(Cm.shapes(spec), Cm.FIELDS)))
-        else:
-            Cm.check_out(out, self.num_envs, spec, self.device)
+        out = self._fresh_out(Cm, Cm.Camera, Cm.shapes(spec), spec, mask) if out is None else Cm.check_out(out, self.num_envs, spec, self.device)
         self._sensor_launch('_last_camera_mask', mask, lambda m, stream: Cm.camera(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
@@ -364,12 +349,7 @@ class BatchedEnv:
         from . import links_device as Lk
         if spec is None:
             spec = self._default_spec('links', lambda: Lk.default_spec(self.cfg))
-        if out is None:
-            if not Lk.sized(spec):   # (the library refuses it too; no tensor can be shaped after it)
-                raise ValueError(f'spec.n_sites must be within 0..{Lk.MAX_SITES}, got {spec.n_sites}')
-            out = Lk.Links(*(self._fresh(mask, shape, dtype) if shape[0] else None for shape, (_, dtype) in zip(Lk.shapes(self.cfg, spec), Lk.FIELDS)))
-        else:
-            Lk.check_out(out, self.num_envs, self.cfg, spec, self.device)
+        out = self._fresh_out(Lk, Lk.Links, Lk.shapes(self.cfg, spec), spec, mask) if out is None else Lk.check_out(out, self.num_envs, self.cfg, spec, self.device)
         self._sensor_launch('_last_links_mask', mask, lambda m, stream: Lk.links(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 

@@ -64,6 +64,12 @@ def test_output_guards():
         for _ in range(3):   # 1, 2 and 3 bytes past a multiple of 4
             c.addr[output] += 1
             c.refused(f'{output} must be 4-byte aligned')
+    for first, second in (('depth', 'rgb'), ('seg', 'rgb'), ('depth', 'seg')):   # of two, the first in the record's order is named
+        c = Call()
+        c.addr[first] += 2
+        c.addr[second] += 1
+        c.refused(f'{first} must be 4-byte aligned')
+        assert c.last_error() == f'hrl_camera: {first} must be 4-byte aligned'
     c = Call()
     for output in OUTPUTS:
         c.addr[output] = None
@@ -134,5 +140,12 @@ def test_check_out_on_host_tensors():
         Cm.check_out(out._replace(rgb=unaligned((N, 24, 48, 3), torch.uint8, 2)), N, spec, cpu)
     with pytest.raises(ValueError, match='out.depth and out.seg must not be the same memory'):
         Cm.check_out(out._replace(seg=out.depth.view(torch.int32)), N, spec, cpu)
+    # every member's own check comes before the same-memory rule, in the record's order
+    with pytest.raises(ValueError, match='out.rgb must be 4-byte aligned'):
+        Cm.check_out(Cm.Camera(out.depth, out.depth.view(torch.int32), unaligned((N, 24, 48, 3), torch.uint8, 2)), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.depth must be 4-byte aligned'):
+        Cm.check_out(Cm.Camera(unaligned((N, 24, 48), torch.float32, 2), out.seg, unaligned((N, 24, 48, 3), torch.uint8, 1)), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.depth and out.seg must not be the same memory'):
+        Cm.check_out(Cm.Camera(out.depth, out.depth.view(torch.int32), out.depth.view(torch.uint8).flatten()[:N * 24 * 48 * 3].view(N, 24, 48, 3)), N, spec, cpu)   # all three: the first pair
     assert Cm.sized(spec) and not Cm.sized(Cm.hrl_camera_spec(width=256, height=24)) and not Cm.sized(Cm.hrl_camera_spec(width=48, height=0))
 

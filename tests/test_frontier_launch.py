@@ -68,6 +68,12 @@ def test_output_and_memory_guards():
         c.refused(f'{name} must be 4-byte aligned')
         c.addr[name] += 1
         c.refused(f'{name} must be 4-byte aligned')
+    for first, second in (('edge', 'seen'), ('cell', 'seen'), ('dist', 'goal')):   # of two, the first in the record's order is named; `seen` comes last
+        c = Call()
+        c.addr[first] += 2
+        c.addr[second] += 1
+        c.refused(f'{first} must be 4-byte aligned')
+        assert c.last_error() == f'hrl_frontier: {first} must be 4-byte aligned'
     c = Call()
     for output in OUTPUTS:
         c.addr[output] = None
@@ -150,4 +156,6 @@ def test_check_seen_and_check_out_on_host_tensors():
         X.check_out(out._replace(edge=seen), N, spec, cpu, seen)
     with pytest.raises(ValueError, match='out.parent and seen must not be the same memory'):
         X.check_out(out._replace(parent=seen), N, spec, cpu, seen)
+    with pytest.raises(ValueError, match='out.cell must be 4-byte aligned'):   # every member's own check comes before the rule about `seen`
+        X.check_out(out._replace(edge=seen, cell=unaligned((N,), torch.int32, 2)), N, spec, cpu, seen)
     assert F.MIN_SIZE == X.MIN_SIZE and F.MAX_SIZE == X.MAX_SIZE

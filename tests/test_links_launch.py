@@ -64,6 +64,12 @@ def test_output_guards():
         for _ in range(3):   # 1, 2 and 3 bytes past a multiple of 4
             c.addr[output] += 1
             c.refused(f'{output} must be 4-byte aligned')
+    for first, second in (('origin', 'com'), ('quat', 'site_vel'), ('ang_vel', 'site_pos')):   # of two, the first in the record's order is named
+        c = Call()
+        c.addr[first] += 2
+        c.addr[second] += 1
+        c.refused(f'{first} must be 4-byte aligned')
+        assert c.last_error() == f'hrl_links: {first} must be 4-byte aligned'
     c = Call()
     for output in OUTPUTS:
         c.addr[output] = None
@@ -146,6 +152,13 @@ def test_check_out_on_host_tensors():
         Lk.check_out(out._replace(lin_vel=unaligned((N, 13, 3), torch.float32, 2)), N, cfg, spec, cpu)
     with pytest.raises(ValueError, match='out.origin and out.com must not be the same memory'):
         Lk.check_out(out._replace(com=out.origin), N, cfg, spec, cpu)
+    with pytest.raises(ValueError, match='out.lin_vel must be 4-byte aligned'):   # every member's own check comes before the same-memory rule
+        Lk.check_out(out._replace(com=out.origin, lin_vel=unaligned((N, 13, 3), torch.float32, 2)), N, cfg, spec, cpu)
+    with pytest.raises(ValueError, match='out.origin and out.com must not be the same memory'):   # the first pair in the record's order
+        Lk.check_out(out._replace(com=out.origin, ang_vel=out.origin, site_vel=out.site_pos), N, cfg, spec, cpu)
+    none = Lk.default_spec(cfg, 'world', ())
+    empty = torch.zeros(N, 0, 3)
+    assert Lk.check_out(Lk.Links(origin=out.origin, site_pos=empty, site_vel=empty), N, cfg, none, cpu).site_vel is empty   # empty tensors share their (null) address
     point = _lib.default_config(K.HRL_POINT_GATHER, num_envs=N)
     assert Lk.shapes(point, Lk.default_spec(point)) == ((1, 3), (1, 3), (1, 4), (1, 3), (1, 3), (1, 3), (1, 3))
     assert Lk.sized(spec) and not Lk.sized(Lk.hrl_links_spec(n_sites=17)) and not Lk.sized(Lk.hrl_links_spec(n_sites=-1))

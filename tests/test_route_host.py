@@ -329,6 +329,24 @@ def test_bad_specs_are_refused_with_a_reason(field, value):
     assert all((x == -7).all() for x in out)
 
 
+def test_two_misaligned_pointers_name_the_first():
+    """The outputs are looked at in the record's order and `starts` after them: of two misaligned pointers the first is named."""
+    cfg, state, items, aux = shard(K.HRL_ANT_FLAT)
+    spec = R.default_spec(cfg, n_starts=2)
+    b = K.make_buffers(rt.ptr(state), rt.ptr(items), rt.ptr(aux), None, None, None, None, None)
+    room = {name: np.zeros(N * 2 * 16 * 2 * 4 + 64, np.uint8) for name in rt.NAMES + ('starts',)}
+    at = {name: (a.ctypes.data + 63) // 64 * 64 for name, a in room.items()}
+    L = R.lib()
+    for first, second in (('waypoints', 'starts'), ('count', 'cells'), ('cells', 'starts')):
+        addr = dict(at)
+        addr[first] += 2
+        addr[second] += 1
+        o = R.hrl_route_out(**{name: addr[name] for name in rt.NAMES})
+        assert L.hrl_route(C.byref(cfg), C.byref(b), C.byref(spec), addr['starts'], None, C.byref(o), None) == K.HRL_ERR_BAD_ARG
+        assert L.hrl_route_last_error().decode() == f'hrl_route: {first} must be 4-byte aligned'
+    assert all((a == 0).all() for a in room.values())
+
+
 def test_default_spec_and_the_mirrors():
     for kind in rt.KINDS:
         cfg = orc.default_config(kind, num_envs=1)

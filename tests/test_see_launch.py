@@ -66,6 +66,12 @@ def test_output_guards():
         c.refused(f'{output} must be 4-byte aligned')
         c.addr[output] += 1
         c.refused(f'{output} must be 4-byte aligned')
+    for first, second in (('visible', 'seen'), ('seen', 'fresh')):   # of two, the first in the record's order is named
+        c = Call()
+        c.addr[first] += 2
+        c.addr[second] += 1
+        c.refused(f'{first} must be 4-byte aligned')
+        assert c.last_error() == f'hrl_see: {first} must be 4-byte aligned'
     c = Call()
     for output in OUTPUTS:
         c.addr[output] = None
@@ -131,4 +137,15 @@ def test_check_out_on_host_tensors():
         V.check_out(out._replace(seen=None), N, spec, cpu)
     with pytest.raises(ValueError, match='out.visible and out.seen must not be the same memory'):
         V.check_out(out._replace(seen=out.visible), N, spec, cpu)
+    # the members' own checks come before the three rules, in the record's order
+    with pytest.raises(TypeError, match='out.visible must be a torch.uint8 tensor'):
+        V.check_out(V.See(out.visible.float(), None, out.fresh), N, spec, cpu)
+    with pytest.raises(ValueError, match=r'out.visible must be contiguous \(2, 40, 24\)'):
+        V.check_out(V.See(torch.zeros(N, 24, 40, dtype=torch.uint8), None, out.fresh), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.fresh must be 4-byte aligned'):
+        V.check_out(V.See(out.visible, None, unaligned((N,), torch.int32, 2)), N, spec, cpu)
+    with pytest.raises(ValueError, match='out.visible must be 4-byte aligned'):
+        V.check_out(V.See(unaligned((N, 40, 24), torch.uint8, 1), unaligned((N, 40, 24), torch.uint8, 2), out.fresh), N, spec, cpu)
+    with pytest.raises(ValueError, match='out holds no tensor'):
+        V.check_out(V.See(), N, V.default_spec(cfg, 'ego', 24, 40), cpu)
     assert F.MIN_SIZE == V.MIN_SIZE and F.MAX_SIZE == V.MAX_SIZE

@@ -1,5 +1,6 @@
-"""The guards that the four sensor libraries (libhrl_{render,scan,probe,field}_hip.so) share: what their launchers refuse before they look
-for a device, and what the Python bindings refuse before they call.  CPU only: every call below returns before the HIP runtime is asked
+"""The guards that the nine sensor libraries share (csrc/sensor_launch.h, _sensor.py), on the first four of them
+(libhrl_{render,scan,probe,field}_hip.so; the others have test_route_host.py and test_{see,frontier,camera,links}_launch.py in this form):
+what their launchers refuse before they look for a device, and what the Python bindings refuse before they call.  CPU only: every call below returns before the HIP runtime is asked
 anything, so the results are the same with and without a GPU.  The phrases are copied from csrc/*_hip.hip and csrc/*_core.h."""
 import ctypes as C
 
@@ -104,10 +105,28 @@ def test_probe_points_guards():
     c.refused('points must be 8-byte aligned')
     c.addr['points'] = None
     c.refused('null points')
+    for output in OUTPUTS['probe']:   # `points` is looked at before the outputs
+        c = Call('probe')
+        c.addr['points'] += 4
+        c.addr[output] += 1
+        c.refused('points must be 8-byte aligned')
+        assert c.last_error() == 'hrl_probe: points must be 8-byte aligned'
+        c.addr['points'] = None
+        c.refused('null points')
+    c = Call('probe')   # and of two outputs the first in the record's order is named
+    c.addr['clearance'] += 2
+    c.addr['via'] += 1
+    c.refused('clearance must be 4-byte aligned')
+    assert c.last_error() == 'hrl_probe: clearance must be 4-byte aligned'
+    c = Call('field')
+    c.addr['dist'] += 2
+    c.addr['parent'] += 1
+    c.refused('dist must be 4-byte aligned')
+    assert c.last_error() == 'hrl_field: dist must be 4-byte aligned'
 
 
 def test_a_refusal_stays_in_its_own_library():
-    """The four libraries live in one process; each keeps its own error string."""
+    """The libraries live in one process; each keeps its own error string (four of the nine here)."""
     calls = {name: Call(name) for name in NAMES}
     for c in calls.values():
         c.refused('null buffer record', record=False)
