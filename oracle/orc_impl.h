@@ -1597,6 +1597,12 @@ static void FN(stored_feet)(const hrl_config *cfg, const int32_t *aux, REAL *fee
     for (int l = 0; l < 4; ++l) feet[l] = (on && (((uint32_t)aux[1] >> (28 + l)) & 1u)) ? R_(1) : R_(0);
 }
 /* observation of the CURRENT state (used by reset and by step) for ant kinds that do not need step-only data */
+/* maze kinds: the episode's target is entry aux[3] of the constructor's `targets` (ant_maze_bullet_env.py:114-115); the caller owns `aux`, and an
+ * index outside the table reads entry 0 (csrc/step_core.h maze_target) */
+#ifndef ORC_TARGET_INDEX
+#define ORC_TARGET_INDEX
+static inline int orc_target_index(int32_t aux3) { return (uint32_t)aux3 < (uint32_t)HRL_MAX_TARGETS ? (int)aux3 : 0; }
+#endif
 static void FN(make_obs)(const FN(orc_env) * E, const REAL *st, const REAL *items, const int32_t *aux, const REAL *feet,
                          REAL *obs, REAL *wtd_out, int *nlim_out, REAL *s28_out, REAL *centroid_out) {
     const hrl_config *cfg = &E->cfg;
@@ -1609,7 +1615,7 @@ static void FN(make_obs)(const FN(orc_env) * E, const REAL *st, const REAL *item
     }
     REAL s28[28], rpy[3], wtd, tgt[2] = {R_(cfg->walk_target[0]), R_(cfg->walk_target[1])};
     int nlim;
-    if (cfg->env_kind == HRL_ANT_MAZE || cfg->env_kind == HRL_ANT_MAZE_MJ) { tgt[0] = R_(cfg->targets[aux[3]][0]); tgt[1] = R_(cfg->targets[aux[3]][1]); }
+    if (cfg->env_kind == HRL_ANT_MAZE || cfg->env_kind == HRL_ANT_MAZE_MJ) { tgt[0] = R_(cfg->targets[orc_target_index(aux[3])][0]); tgt[1] = R_(cfg->targets[orc_target_index(aux[3])][1]); }
     if (cfg->env_kind == HRL_ANT_FLAGRUN) FN(flag_current_goal)(cfg, items, aux, tgt);
     FN(orc_ant_calc_state)(cfg, &E->K, st, st + HRL_QVEL_OFF, st[HRL_INITZ_OFF], tgt, feet, s28, &nlim, &wtd, rpy, centroid_out);
     if (wtd_out) *wtd_out = wtd;
@@ -1649,7 +1655,7 @@ void FN(orc_env_reset_one)(const FN(orc_env) * E, int64_t env, REAL *st, REAL *i
     /* what the robot was walking towards before this reset (see orc_reset_potential) */
     REAL prev_target[2] = {R_(cfg->walk_target[0]), R_(cfg->walk_target[1])};
     if (ep > 0) {
-        if (maze_kind) { prev_target[0] = R_(cfg->targets[aux[3]][0]); prev_target[1] = R_(cfg->targets[aux[3]][1]); }
+        if (maze_kind) { prev_target[0] = R_(cfg->targets[orc_target_index(aux[3])][0]); prev_target[1] = R_(cfg->targets[orc_target_index(aux[3])][1]); }
         if (cfg->env_kind == HRL_ANT_FLAGRUN) FN(flag_current_goal)(cfg, items, aux, prev_target);
     }
     for (int i = 0; i < HRL_STATE_STRIDE; ++i) st[i] = 0;
@@ -1845,7 +1851,7 @@ void FN(orc_env_step_one)(const FN(orc_env) * E, int64_t env, REAL *st, REAL *it
             goal_out[0] = g2[0]; goal_out[1] = g2[1]; goal_out[2] = retarget ? R_(1) : R_(0); goal_out[3] = R_(steps);
         }
     } else if (cfg->env_kind == HRL_ANT_MAZE_MJ) { /* MjAnt.py:36-97 then ant_maze_mj_env.py:66-78 */
-        REAL wtd, s28[28], rpy[3], inner, tgt[2] = {R_(cfg->targets[aux[3]][0]), R_(cfg->targets[aux[3]][1])};
+        REAL wtd, s28[28], rpy[3], inner, tgt[2] = {R_(cfg->targets[orc_target_index(aux[3])][0]), R_(cfg->targets[orc_target_index(aux[3])][1])};
         int nlim, idone;
         FN(orc_ant_calc_state)(cfg, K, st, st + HRL_QVEL_OFF, st[HRL_INITZ_OFF], tgt, feet, s28, &nlim, &wtd, rpy, 0);
         REAL pot = -wtd / (K->h * R_(K->nsub));
@@ -1854,7 +1860,7 @@ void FN(orc_env_step_one)(const FN(orc_env) * E, int64_t env, REAL *st, REAL *it
         st[HRL_POTENTIAL_OFF] = pot;
         FN(orc_maze_mj_task)(cfg, st, rpy[2], inner, idone, wtd, aux[0], &FN(maze_lines)[0][0], 7, obs, &rew, &done);
     } else { /* maze: upstream WalkerBaseBulletEnv.step then ant_maze_bullet_env.py:77-97 */
-        REAL wtd, s28[28], rpy[3], tgt[2] = {R_(cfg->targets[aux[3]][0]), R_(cfg->targets[aux[3]][1])};
+        REAL wtd, s28[28], rpy[3], tgt[2] = {R_(cfg->targets[orc_target_index(aux[3])][0]), R_(cfg->targets[orc_target_index(aux[3])][1])};
         int nlim;
         FN(orc_ant_calc_state)(cfg, K, st, st + HRL_QVEL_OFF, st[HRL_INITZ_OFF], tgt, feet, s28, &nlim, &wtd, rpy, 0);
         REAL alive = (s28[0] + st[HRL_INITZ_OFF] > R_(0.26)) ? R_(1) : R_(-1);

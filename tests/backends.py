@@ -6,6 +6,7 @@ the fuzz tools, the fixture replay, the fingerprint) drives the oracle and any o
 
     state items aux obs rew done info final_obs truncated [goal, solver_rows]   numpy arrays;   N od ad cfg
     reset(mask=None)  step(a)  observe(mask=None)  set_goals(goals, mask=None)  next_target(mask=None) -> ok  push(o)  fill(name, v)  close()
+    give_items(given)                                                           an items record or NULL in the buffer record
     set(qpos, qvel, items=None, aux3=None, initial_z=None)                      the teleport of tests/golden_replay.py
 
 Importing this module needs no GPU: torch and the HIP library are loaded by Device() only.  Test infrastructure only."""
@@ -69,6 +70,10 @@ class Emu(emu_env.EmuEnv):
         assert emu_env.lib(self.asan).emu_next_target(C.byref(self.cfg), C.byref(self._bufs()), orc.ptr(mask), orc.ptr(ok), self.reverse) == 0
         return ok
 
+    def give_items(self, given):
+        """hand the step an items record (True) or NULL (False): only the kinds that keep nothing there may go without"""
+        self.null_items = not given
+
     def close(self):
         pass
 
@@ -101,7 +106,7 @@ class Device:
         a = getattr(self.env, 'reward' if name == 'rew' else name).cpu().numpy()
         # the kinds that keep nothing in the items record hand the library NULL for it (BatchedEnv._uses_items): whatever push() left in the tensor
         # is never read or written by a launch, and the oracle's record of such a kind stays zero
-        return np.zeros_like(a) if name == 'items' and not self.env._uses_items else a
+        return np.zeros_like(a) if name == 'items' and self.env._bufs.items is None else a
 
     def reset(self, mask=None):
         self.env.reset(self._dev(mask))
@@ -134,6 +139,12 @@ class Device:
 
     def next_target(self, mask=None):
         return self.env.next_target(self._dev(mask))[1].cpu().numpy()
+
+    def give_items(self, given):
+        """hand the library an items record (True) or NULL (False) through the C ABI's buffer record"""
+        e = self.env
+        assert given or not e._uses_items
+        e._bufs.items = e.items.data_ptr() if given else None
 
     def close(self):
         self.env.close()

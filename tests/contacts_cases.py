@@ -26,6 +26,10 @@ _LIB = None
 def lib():
     """tests/emu/libhrl_emu_contacts.so: emu_lib.cpp + emu_step_contacts, built with the flags of tests/emu/Makefile."""
     global _LIB
+    if _LIB is None and emu_env.coverage_dir():   # tests/tools/step_coverage.py: the Makefile's --coverage build of the same source
+        d, cov = os.path.join(ROOT, 'tests', 'emu'), emu_env.coverage_dir()
+        subprocess.check_call(['make', '-s', '-C', d, 'COVDIR=' + cov, os.path.join(cov, 'libhrl_emu_contacts_cov.so')])
+        _LIB = C.CDLL(os.path.join(cov, 'libhrl_emu_contacts_cov.so'))
     if _LIB is None:
         d = os.path.join(ROOT, 'tests', 'emu')
         out, src = os.path.join(d, 'libhrl_emu_contacts.so'), os.path.join(d, 'emu_contacts.cpp')

@@ -12,12 +12,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIBS = {}
 
 
+def coverage_dir():
+    """HRL_EMU_COVERAGE=<directory>, set by tests/tools/step_coverage.py alone: load the --coverage builds of the Makefile from there (their
+    counts land next to them); unset, as in every test run, nothing changes"""
+    d = os.environ.get('HRL_EMU_COVERAGE')
+    return os.path.abspath(d) if d else None
+
+
 def lib(asan=False):
     name = 'libhrl_emu_asan.so' if asan else 'libhrl_emu.so'
     if name not in _LIBS:
         d = os.path.join(ROOT, 'tests', 'emu')
-        subprocess.check_call(['make', '-s', '-C', d, name])
-        _LIBS[name] = C.CDLL(os.path.join(d, name))
+        cov = None if asan else coverage_dir()
+        if cov:
+            path = os.path.join(cov, 'libhrl_emu_cov.so')
+            subprocess.check_call(['make', '-s', '-C', d, 'COVDIR=' + cov, path])
+        else:
+            path = os.path.join(d, name)
+            subprocess.check_call(['make', '-s', '-C', d, name])
+        _LIBS[name] = C.CDLL(path)
         _LIBS[name].emu_validate.restype = C.c_char_p
     return _LIBS[name]
 
@@ -29,6 +42,7 @@ def ptr(a):
 class EmuEnv:
     def __init__(self, cfg, reverse=False, asan=False):
         self.cfg, self.reverse, self.asan = cfg, int(reverse), asan
+        self.null_items = False   # True: the buffer record carries NULL for `items` (include/hrl_envs.h: the kinds that keep nothing there)
         L = lib(asan)
         n = cfg.num_envs
         self.N, self.od, self.ad = n, L.emu_obs_dim(C.byref(cfg)), L.emu_act_dim(C.byref(cfg))
@@ -47,7 +61,7 @@ class EmuEnv:
         self.solver_rows = np.zeros(n, np.int32)
 
     def _bufs(self):
-        return K.make_buffers(ptr(self.state), ptr(self.items), ptr(self.aux), ptr(self.act), ptr(self.obs),
+        return K.make_buffers(ptr(self.state), None if self.null_items else ptr(self.items), ptr(self.aux), ptr(self.act), ptr(self.obs),
                               ptr(self.rew), ptr(self.done), ptr(self.info), ptr(self.final_obs), ptr(self.truncated), ptr(self.goal), ptr(self.solver_rows))
 
     def reset(self, mask=None):

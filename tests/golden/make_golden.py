@@ -1139,6 +1139,95 @@ def main():
         'player_cube': mj_body(cube.find('worldbody/body')),
         'box': urdf_box('box.xml'), 'food': urdf_box('food.xml'), 'poison': urdf_box('poison.xml'), 'wall': urdf_box('wall.xml'), 'plane': urdf_box('plane.xml')}
 
+    # ---------------------------------------------------------------- the observation rules at their edges (tests/STEP_COVERAGE.md)
+    # An independent witness for the branches the directed parity scenarios enter: the reference's own get_sensor_readings (the angle fold of
+    # ant_gather_env.py:148-155 and the bin index of :161) and segment_intersection (intersection_utils.py) on inputs that are exactly
+    # representable in fp32 and whose decisions rest on exact zeros and equalities.  Replayed with ZERO excused readings, so every case's deciding
+    # quantities -- the folded angle, inside the span or not, the bin -- are evaluated here in numpy once in float64 and once in float32, and a
+    # case where the two disagree is dropped, loudly; so is a case on which the reference itself fails (it has no clamp for the bin index: an
+    # angle exactly on the last bin's upper edge is an IndexError there whenever the quotient comes out as n_bins).
+    def fold_and_bin(ft, dx, dy, yaw, span, n_bins):
+        two_pi, pi = ft(2 * math.pi), ft(math.pi)
+        a = ft(np.arctan2(ft(dy), ft(dx))) - ft(yaw)
+        a = ft(np.fmod(a, two_pi)) if not abs(a) < two_pi else a      # python's % (2 pi) ...
+        a = ft(a + two_pi) if a < 0 else a
+        a = ft(a - two_pi) if a >= two_pi else a                       # ... whose result lies in [0, 2 pi)
+        a = ft(a - two_pi) if a > pi else a
+        half = ft(span) * ft(0.5)
+        inside = bool(abs(a) <= half)
+        return float(a), inside, (min(int(ft(a + half) / (ft(span) / ft(n_bins))), n_bins - 1) if inside else -1)
+
+    def edge_sensor_case(name, cls, n_bins, span, srange, yaw, item, comment):
+        assert all(float(np.float32(v)) == v for v in (srange,) + tuple(item)), name   # (pi itself is pi in either format: yaw +-pi, the spans)
+        a64, in64, b64 = fold_and_bin(np.float64, item[0], item[1], yaw, span, n_bins)
+        a32, in32, b32 = fold_and_bin(np.float32, item[0], item[1], yaw, span, n_bins)
+        if in64 != in32 or b64 != b32 or abs(a64 - a32) > 1e-6:
+            print('obs_edges: DROPPED %s (n_bins %d): float64 and float32 disagree on the deciding quantities: %r / %r' % (name, n_bins, (a64, in64, b64), (a32, in32, b32)))
+            return None
+        far = [60.0, 60.0, 0.1]
+        food = {11 + i: ([float(item[0]), float(item[1]), 0.1] if i == 0 else list(far)) for i in range(2)}
+        poison = {13 + i: ([float(item[0]), float(item[1]), 0.1] if i == 1 else list(far)) for i in range(2)}   # the same place, as the other type's second item
+        body = Body([0.0, 0.0, 0.5], [0.0, 0.0, yaw])
+        scene = NS(food=food, poison=poison, all_items={**food, **poison})
+        if cls is AntGatherBulletEnv:
+            self = NS(n_bins=n_bins, sensor_span=span, sensor_range=srange, robot_body=body, stadium_scene=scene, FOOD='food', POISON='poison', debug=False, parts={'torso': body})
+        else:
+            self = NS(n_bins=n_bins, sensor_span=span, sensor_range=srange, robot=NS(robot_body=body), stadium_scene=scene, FOOD='food', POISON='poison', debug=False)
+        dists = {i: cls.sq_dist_robot(self, p) for i, p in scene.all_items.items()}
+        try:
+            fr, pr = cls.get_sensor_readings(self, dists)
+        except IndexError:
+            print('obs_edges: DROPPED %s (n_bins %d): the reference itself raises IndexError (bin index == n_bins, it has no clamp)' % (name, n_bins))
+            return None
+        assert (b64 >= 0) == bool(np.any(fr > 0)) and (b64 < 0 or (fr[b64] > 0 and pr[b64] > 0)), name   # the reference decided as computed above
+        return {'name': name, 'comment': comment, 'cls': cls.__name__, 'n_bins': n_bins, 'span': span, 'range': srange, 'robot_xy': [0.0, 0.0], 'yaw': float(yaw),
+                'food': [food[k][:2] for k in food], 'poison': [poison[k][:2] for k in poison], 'folded_angle': a64, 'bin': b64,
+                'food_readings': tolist(fr), 'poison_readings': tolist(pr)}
+
+    tiny = 2.0 ** -23
+    PI_, TWO_PI_ = np.pi, 2 * np.pi
+    edge_inputs = [   # (name, yaw, item, the spans the name is true for, comment)
+        # fp32 and fp64 legitimately differ in the intermediate here and agree in the result: -4e-8 + 2 pi rounds to 2 pi in fp32 and is folded back
+        # to 0, float64 carries -4e-8 through -- -epsilon against 0, far inside the tolerance, and the same bin as long as 0 is no bin edge
+        ('tiny_negative', 0.0, (3.0, -tiny), (PI_, TWO_PI_), 'a + 2 pi rounds to 2 pi in fp32; -eps (fp64) against 0 (fp32), same bin'),
+        ('two_pi_before_the_fold', -np.pi, (-3.0, 0.0), (PI_, TWO_PI_), 'pi - (-pi) = 2 pi exactly, in both formats; folds to 0'),
+        ('below_minus_pi', np.pi, (-3.0, -tiny), (PI_, TWO_PI_), '(-pi + eps) - pi; folds to eps (fp64) / 0 (fp32)'),
+        ('minus_three_half_pi', np.pi, (0.0, -3.0), (PI_,), '-pi / 2 - pi folds to + pi / 2, the upper edge of a span of pi'),
+        ('top_edge', 0.0, (0.0, 3.0), (PI_,), 'atan2(3, 0) = pi / 2 = span / 2 exactly: the last bin, upper edge included'),
+        ('bottom_edge', 0.0, (0.0, -3.0), (PI_,), '- span / 2 exactly: bin 0'),
+        ('just_outside', 0.0, (-tiny * 4, 3.0), (PI_,), 'a hair beyond + span / 2: no reading'),
+        ('behind_outside', 0.0, (-3.0, 0.0), (PI_,), 'atan2(0, -3) = + pi, not folded (a > pi is false): outside a span of pi, no reading'),
+        ('behind_top_edge', 0.0, (-3.0, 0.0), (TWO_PI_,), 'atan2(0, -3) = + pi = span / 2 exactly: the last bin of a span of 2 pi, upper edge included'),
+        ('quarter_turn', 0.0, (0.0, 3.0), (TWO_PI_,), 'pi / 2, an interior angle of a span of 2 pi (an edge of an 8-bin fan, interior to the others)'),
+    ]
+    edges = {'sensor': [], 'segments': [], 'quaternions': []}
+    for cls in (AntGatherBulletEnv, GatherBulletEnv):
+        for name, yaw, item, spans, comment in edge_inputs:
+            for n_bins, span in ((5, np.pi), (7, np.pi), (8, np.pi), (3, np.pi), (5, 2 * np.pi), (8, 2 * np.pi)):
+                if span not in spans:
+                    continue
+                c = edge_sensor_case(name, cls, n_bins, span, 20.0, yaw, item, comment)
+                if c is not None:
+                    edges['sensor'].append(c)
+    # robots standing exactly on the line of an axis-aligned wall of the maze box, targets on it too: the collinear rules decide on exact zeros
+    box_lines = [(a, b) for a, b in maze.bounds[4:7]]
+    for robot, target in [((1, 3), (1, 5)), ((1, 3), (1, 0)), ((1, -3), (1, 0)), ((1, 0), (1, 1)), ((-4, -2), (-3, -2)), ((3, -2), (4.5, -2)), ((3, -2), (0, -2)),
+                          ((1, 2), (3, 2)), ((3, 0), (1, 0)), ((3, 1), (4, 3)), ((3, 0), (-1, 0))]:
+        per_line = [bool(iu.segment_intersection(P(*map(float, robot)), P(*map(float, target)), a, b)) for a, b in box_lines]
+        edges['segments'].append({'robot': list(map(float, robot)), 'target': list(map(float, target)), 'per_line': per_line, 'hidden': any(per_line)})
+    edges['box_lines'] = [[[a.x, a.y], [b.x, b.y]] for a, b in box_lines]
+    # quat_to_rpy has no code in the reference (pybullet is absent): the replay checks a property instead, on these quaternions -- a yaw, then a
+    # pitch of asin(s) -- from both sides of the lock band's threshold 0.99999, none closer to it than 5e-6 in s
+    for s in (1.0, -1.0, 0.999997, -0.999996, 0.999995, 0.999985, -0.99998, 0.9, -0.5, 0.0):
+        for yaw in (0.0, np.pi / 2, -np.pi / 2, np.pi, 1.0, -2.5):
+            th = math.asin(s)
+            sz, cz, sy, cy = math.sin(yaw / 2), math.cos(yaw / 2), math.sin(th / 2), math.cos(th / 2)
+            q = [float(np.float32(v)) for v in (-sz * sy, cz * sy, cy * sz, cz * cy)]
+            sarg64 = -2.0 * (q[0] * q[2] - q[3] * q[1])
+            assert abs(abs(sarg64) - 0.99999) >= 4e-6, (s, yaw, sarg64)   # (the rounding of the components moves it by ~1e-7)
+            edges['quaternions'].append({'sin_pitch': s, 'yaw': float(yaw), 'quat': q})
+    G['obs_edges'] = edges
+
     only = set(sys.argv[1:])  # optional: names of the fixtures to (re)write; default all
     for name, val in G.items():
         if only and name not in only:

@@ -146,6 +146,115 @@ def replay_all(make_side, default_config):
     return report
 
 
+LOCK = 0.99999   # pybullet getEulerFromQuaternion's gimbal-lock band: |sin(pitch)| >= LOCK
+
+
+def rot_from_quat(q):
+    x, y, z, w = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def rot_from_rpy(r, p, sy, cy):
+    """Rz(yaw) Ry(pitch) Rx(roll), the yaw given by its sine and cosine"""
+    cr, sr, cp, sp = math.cos(r), math.sin(r), math.cos(p), math.sin(p)
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]])
+
+
+def replay_edges(make_side, default_config, half_pi=np.float32(math.pi / 2)):
+    """tests/golden/obs_edges.json -- the reference's get_sensor_readings and segment_intersection at the edges of the angle fold, of the bins and of
+    the collinear rules, on inputs whose decisions are exact in fp32 and in fp64 alike (the generator dropped the others) -- and the property that
+    stands in for the absent getEulerFromQuaternion.  Returns {part: (cases, readings, readings off by more than TOL)}; NONE may be off.
+    `half_pi`: what "pitch is exactly +-pi / 2" means in the side's number format."""
+    g = load('obs_edges')
+    report = {}
+    groups = {}
+    for c in g['sensor']:
+        groups.setdefault((c['cls'], c['n_bins'], c['span'], c['range']), []).append(c)
+    cases = readings = off = 0
+    for (cls, nb, span, rng_), cs in groups.items():
+        n = len(cs)
+        kind, base = (K.HRL_ANT_GATHER, 26) if cls == 'AntGatherBulletEnv' else (K.HRL_POINT_GATHER, 8)
+        s = make_side(default_config(kind, num_envs=n, n_bins=nb, sensor_span=span, sensor_range=rng_, n_food=2, n_poison=2))
+        qpos, qvel = pose_rows(n, [c['robot_xy'] for c in cs], [(0.0, 0.0, c['yaw']) for c in cs], z=0.75 if kind == K.HRL_ANT_GATHER else 0.5)
+        s.set(qpos, qvel, items=np.array([np.array(c['food'] + c['poison'], np.float64).reshape(-1) for c in cs], np.float32))
+        obs = observed(s)
+        for i, c in enumerate(cs):
+            want = c['food_readings'] + c['poison_readings']
+            off += mismatches(obs[i, base:base + len(want)], want); readings += len(want)
+        cases += n
+    report['sensor'] = (cases, readings, off)
+
+    # the target sensor of AntMaze (ant_maze_bullet_env.py:135-178) lights a bin iff no line of the box hides the target: a wide range, so that the
+    # (parts-centroid) distance never hides it
+    cs = g['segments']
+    n = len(cs)
+    s = make_side(default_config(K.HRL_ANT_MAZE, num_envs=n, sense_target=1, n_bins=8, sensor_range=30.0, targets=[c['target'] for c in cs]))
+    qpos, qvel = pose_rows(n, [c['robot'] for c in cs], [(0.0, 0.0, 0.0)] * n)
+    s.set(qpos, qvel, aux3=np.arange(n, dtype=np.int32))
+    lit = (observed(s)[:, 26:34] > 0).any(axis=1)
+    report['segments'] = (n, n, int(np.sum(lit != ~np.array([c['hidden'] for c in cs]))))
+
+    # roll, pitch and yaw of the point bot's observation (point_bot.py:48-67: obs[6], obs[7]; the bot stands at (-1, 0), so that the angle to its
+    # walk target (0, 0) is -yaw: obs[1], obs[2] = sin, cos of it).  Outside the lock band the rotation rebuilt from them is the quaternion's; inside,
+    # roll is 0, pitch exactly +-pi / 2 and the yaw that of the other arctangent, evaluated here in float64
+    cs = g['quaternions']
+    n = len(cs)
+    s = make_side(default_config(K.HRL_POINT_GATHER, num_envs=n))
+    qpos = np.zeros((n, 15), np.float32); qpos[:, 0] = -1.0; qpos[:, 2] = 0.5; qpos[:, 3:7] = [c['quat'] for c in cs]
+    s.set(qpos, np.zeros((n, 14), np.float32), items=np.full((n, 32), 40.0, np.float32), initial_z=1.0)
+    obs = np.asarray(observed(s), np.float64)
+    readings = off = locked = 0
+    for i, c in enumerate(cs):
+        x, y, z, w = c['quat']
+        sarg = -2.0 * (x * z - w * y)
+        roll, pitch, syaw, cyaw = obs[i, 6], obs[i, 7], -obs[i, 1], obs[i, 2]
+        if abs(sarg) >= LOCK:
+            yaw = 2.0 * (math.atan2(-x, y) if sarg > 0 else math.atan2(x, -y))
+            off += int(roll != 0.0) + int(pitch != math.copysign(float(half_pi), sarg)) + mismatches([syaw, cyaw], [math.sin(yaw), math.cos(yaw)])
+            readings += 4; locked += 1
+        else:
+            off += mismatches(rot_from_rpy(roll, pitch, syaw, cyaw), rot_from_quat(c['quat'])); readings += 9
+    report['quaternions'] = (n, readings, off)
+    assert locked >= 24 and n - locked >= 24
+    return report
+
+
+def check_edges(report):
+    for name, (cases, readings, off) in report.items():
+        print(f'obs_edges {name}: {cases} cases, {readings} readings, {off} off by more than the tolerance')
+    assert report['sensor'][0] == 52 and report['segments'][0] == 11 and report['quaternions'][0] == 60
+    assert all(off == 0 for _, _, off in report.values()), report   # no excused reading: every decision of these inputs is exact
+
+
+class OracleSide:
+    """the CPU oracle (tests/orc.py) behind the two calls of a replay side, in float64 or float32"""
+
+    def __init__(self, cfg, dtype):
+        import orc
+        self.o = orc.OracleEnv(cfg, dtype)
+        self.o.reset()
+
+    def set(self, qpos, qvel, items=None, aux3=None, initial_z=None):
+        o = self.o
+        o.state[:, 0:15] = qpos; o.state[:, 15:29] = qvel
+        if initial_z is not None:
+            o.state[:, K.HRL_INITZ_OFF] = initial_z
+        if items is not None:
+            o.items[:, :items.shape[1]] = items
+        if aux3 is not None:
+            o.aux[:, 3] = aux3
+
+    def observe(self):
+        return self.o.observe()
+
+    def close(self):
+        pass
+
+
 def check(report):
     for name, (cases, readings, off) in report.items():
         print(f'{name}: {cases} cases, {readings} readings, {off} off by more than the tolerance')

@@ -5,6 +5,7 @@ oracle's edited pre-step buffers into every side (push), compares all nine buffe
 `make(kind, count_rows=False, **over) -> [sides]` is the suite's factory (tests/backends.py): tests/test_emu_parity.py hands back the host executor
 in both lane orders (the second is also compared with the first), tests/test_gpu_parity.py the device.  Sizes and the coverage thresholds
 (`need`: counter -> least value) are the suite's own; a threshold is a condition on the inputs.  Test infrastructure only."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -520,3 +521,397 @@ def second_support_points(make, n, rounds, stride, maze, gather):
                 step(o, sides, uniform(rng, n, 8, 0.2), (group, t, k), names=names)
                 paid += int((o.info[:, 0] != 0).sum())
         covered(need, seconds=seconds, paid=paid)
+
+
+# ------------------------------------------------------------------------------------------------ directed scenarios (tests/STEP_COVERAGE.md)
+# Branches of csrc/step_core.h that no rollout enters: each scenario places the states that enter one, compares observe() and a step() of all sides
+# with the oracle bit for bit, and counts -- from the oracle's records and the oracle's own functions, in fp32 -- that the case really occurred.
+ANTS = (K.HRL_ANT_FLAT, K.HRL_ANT_GATHER, K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ, K.HRL_ANT_FLAGRUN)
+F = np.float32
+TWO_PI, PI, HALF_PI = F(6.283185307179586), F(3.141592653589793), F(1.5707963267948966)
+LOCK = F(0.99999)   # pybullet getEulerFromQuaternion's gimbal-lock band
+
+
+def observe(o, sides, tag):
+    """the observation of the oracle's records as they stand, on every side (hrl_observe): nothing else may change"""
+    o.observe()
+    for s in sides:
+        s.push(o); s.observe()
+    check(o, sides, tag, names=('state', 'items', 'aux', 'obs'))
+
+
+def spec_atan2(y, x):
+    """the oracle's atan2 of fp32 arrays"""
+    y, x = np.broadcast_arrays(np.asarray(y, F), np.asarray(x, F))
+    y, x = np.ascontiguousarray(y).ravel(), np.ascontiguousarray(x).ravel()
+    out = np.zeros(len(y), F)
+    orc.lib().orc_spec_math_f32(2, orc.ptr(y), orc.ptr(x), orc.ptr(out), len(y))
+    return out
+
+
+def sarg32(quat):
+    """sin(pitch) as getEulerFromQuaternion forms it, operation by operation in fp32"""
+    x, y, z, w = (quat[:, k].astype(F) for k in range(4))
+    return F(-2.0) * (x * z - w * y)
+
+
+def yaw32(quat):
+    """the yaw of a quaternion outside the lock band, operation by operation in fp32"""
+    x, y, z, w = (quat[:, k].astype(F) for k in range(4))
+    return spec_atan2(F(2.0) * (x * y + w * z), ((w * w + x * x) - y * y) - z * z)
+
+
+def yaw_pitch_quat(yaw, sin_pitch):
+    """(x, y, z, w) of a yaw about z after a pitch about y, in fp64 and rounded once: sarg of it is sin(pitch) to an ulp or two"""
+    yaw, th = np.asarray(yaw, np.float64), np.arcsin(np.asarray(sin_pitch, np.float64))
+    sz, cz, sy, cy = np.sin(yaw / 2), np.cos(yaw / 2), np.sin(th / 2), np.cos(th / 2)
+    return np.stack([-sz * sy, cz * sy, cy * sz, cz * cy], 1).astype(F)
+
+
+def at_rest(o, z):
+    o.state[:, 2] = z; o.state[:, 7:15] = 0; o.state[:, 15:29] = 0
+
+
+def gimbal_lock(make, kind, n, need, **over):
+    """Torsos pitched +-90 degrees: sarg exactly +-1, inside the lock band without being 1, and 0.99998 -- just outside -- as the control, at several
+    yaws.  In the band roll is 0, pitch exactly +-pi/2 and the yaw comes from the other arctangent; they feed the observation, the maze ray fan and
+    the item sensor.  The step from there is a contact case of its own: a tipped ant lies on its legs."""
+    o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=0, **over)
+    # sarg is EXACTLY +-1 in fp32 only where all four components are +-0.5 (a yaw of +-90 degrees; q and -q): sqrt(1/2) squared rounds to 0.49999997.
+    # Env 0 (and 1) hold those, with the sign of the pitch changing from round to round; a pitch of exactly 90 degrees at any other yaw is
+    # 0.99999994, inside the band without being 1, as are +-0.999997; 0.99998 is the control
+    sines = np.array([1.0, -1.0, 1.0, -0.999996, 0.99998] if n >= 5 else [1.0, -0.999997, 0.99998])[:n]
+    yaws = np.array([[np.pi / 2, -np.pi / 2, 0.0, -2.0, 0.5], [-np.pi / 2, np.pi / 2, np.pi, 2.5, -1.0], [np.pi / 2, np.pi / 2, 1.0, 0.1, 2.0]])
+    yaws = yaws[:, :n] if n >= 5 else yaws[:, [0, 3, 4]]
+    rng = np.random.RandomState(2)
+    exact = band = control = 0
+    at = {K.HRL_ANT_GATHER: 4, K.HRL_ANT_MAZE: 4, K.HRL_ANT_FLAGRUN: 6, K.HRL_POINT_GATHER: 6}.get(kind)   # where the observation holds roll, pitch
+    for r, yaw in enumerate(yaws):
+        flip = np.where(np.arange(n) < 2, (-1.0) ** r, 1.0) if n >= 5 else np.where(np.arange(n) < 1, (-1.0) ** r, 1.0)
+        o.state[:, 3:7] = yaw_pitch_quat(yaw, sines * flip) * (-1.0 if r == 2 else 1.0)   # the last round: -q, the same rotations
+        at_rest(o, 0.35 if kind == K.HRL_POINT_GATHER else 0.6)
+        s = np.abs(sarg32(o.state[:, 3:7]))
+        locked = s >= LOCK
+        exact += int((s == 1).sum()); band += int((locked & (s != 1)).sum()); control += int((~locked).sum())
+        observe(o, sides, ('observe', r))
+        if at is not None:
+            assert np.all(o.obs[locked, at] == 0) and np.all(np.abs(o.obs[locked, at + 1]) == HALF_PI) and np.all(np.abs(o.obs[~locked, at + 1]) < HALF_PI), (r, o.obs[:, at:at + 2])
+        step(o, sides, uniform(rng, n, o.ad, 0.3), ('step', r))
+    covered(need, exact=exact, band=band, control=control)
+
+
+def fold32(a):
+    """ant_gather_env.py:148-155 on one fp32 angle, every operation rounded to fp32: python's `% (2 pi)`, then the fold to (-pi, pi]"""
+    a = F(a)
+    if not abs(a) < TWO_PI:
+        a = F(np.fmod(a, TWO_PI))
+    if a < 0:
+        a = F(a + TWO_PI)
+    if a >= TWO_PI:
+        a = F(a - TWO_PI)
+    return F(a - TWO_PI) if a > PI else a
+
+
+# (name, the robot's yaw, the direction robot -> item / target): what the relative angle is BEFORE the fold, in fp32
+ANGLE_CASES = [
+    ('tiny_negative', 0.0, (1.0, -2.5e-8)),            # -2.5e-8: a + 2 pi rounds to 2 pi, which the fold must take back to 0
+    ('tiny_negative', 0.0, (1.0, -1e-7)),
+    ('two_pi_or_more', -np.pi, (-1.0, 1e-8)),          # pi - (-pi) = 2 pi before the `%`
+    ('below_minus_pi', np.pi / 2, (-1.0, -1e-8)),      # -pi - pi / 2
+    ('top_edge', 0.0, None),                           # exactly + span / 2: (angle + span / 2) / bin_res = n_bins, the last bin's upper edge
+]
+
+
+def angle_wraps_and_bin_edges(make, kind, n, need, **over):
+    """The relative angle of the item sensor (gather kinds) / the target sensor (AntMaze with sense_target) at the edges of its fold and of its bins.
+    n_bins is a power of two so that the top edge's quotient is n_bins exactly, whatever the rounding of the division."""
+    maze = kind == K.HRL_ANT_MAZE
+    o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=0, n_bins=8, **(dict(sense_target=1) if maze else {}), **over)
+    half = F(o.cfg.sensor_span) * F(0.5)
+    res = F(o.cfg.sensor_span) / F(8)
+    seen = dict.fromkeys(['tiny_negative', 'two_pi_or_more', 'below_minus_pi', 'top_edge', 'last_bin'], 0)
+    rng = np.random.RandomState(4)
+    for r in range(-(-len(ANGLE_CASES) // n)):
+        cases = [ANGLE_CASES[(r * n + i) % len(ANGLE_CASES)] for i in range(n)]
+        yaw = np.array([c[1] for c in cases])
+        to = np.array([c[2] if c[2] else ((-1.0, 0.0) if maze else (0.0, 1.0)) for c in cases])   # top edge: + pi (span 2 pi) / + pi / 2 (span pi)
+        o.state[:, 3:7] = yaw_pitch_quat(yaw, np.zeros(n))
+        at_rest(o, 0.35 if kind == K.HRL_POINT_GATHER else 0.75)
+        if maze:   # target 1 of the default table, (2, 0): the robot stands 0.4 m from it, clear of the box (x <= 1)
+            o.aux[:, 3] = 1
+            tgt = np.array([2.0, 0.0])
+            o.state[:, 0:2] = (tgt - 0.4 * to).astype(F)
+            d = (tgt.astype(F) - o.state[:, 0:2]).astype(F)
+        else:      # item 0 (a food) 3 m away, all others out of range
+            o.state[:, 0:2] = 0
+            o.items[...] = 90.0
+            o.items[:, 0:2] = (3.0 * to).astype(F)
+            d = (o.items[:, 0:2] - o.state[:, 0:2]).astype(F)
+        a0 = (spec_atan2(d[:, 1], d[:, 0]) - yaw32(o.state[:, 3:7])).astype(F)
+        lit = np.zeros((n, 8), bool)   # the one bin the item / the target must light: it is in range and in sight, so the fold and the bin index ARE reached
+        for i, (name, _, _) in enumerate(cases):
+            a = fold32(a0[i])
+            hit = {'tiny_negative': a0[i] < 0 and F(a0[i] + TWO_PI) >= TWO_PI, 'two_pi_or_more': abs(a0[i]) >= TWO_PI,
+                   'below_minus_pi': a0[i] < -PI, 'top_edge': a == half}[name]
+            seen[name] += int(hit)
+            seen['last_bin'] += int(abs(a) <= half and int(F(a + half) / res) >= 8)
+            if abs(a) <= half:
+                lit[i, min(int(F(a + half) / res), 7)] = True
+        observe(o, sides, ('observe', r))
+        base = 26 if kind != K.HRL_POINT_GATHER else 8   # the food bins / the target bins
+        assert np.array_equal(o.obs[:, base:base + 8] > 0, lit), (r, o.obs[:, base:base + 8], lit)
+        seen['lit'] = seen.get('lit', 0) + int(lit.any(1).sum()); seen['last_bin_lit'] = seen.get('last_bin_lit', 0) + int((o.obs[:, base + 7] > 0).sum())
+        step(o, sides, uniform(rng, n, o.ad, 0.3), ('step', r))
+    covered(need, **seen)
+
+
+def nan_item_in_the_nearest_first_order(make, kind, n, need):
+    """use_sensor=0 (ant_gather_env.py:179-196): a NaN item coordinate has no place in the order by distance -- every output of the item's type is
+    NaN and the episode ends (:101-103); the other type's outputs stay finite"""
+    o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=0, use_sensor=0)
+    nb = 8 if kind == K.HRL_POINT_GATHER else 26
+    m = (o.od - nb) // 2   # outputs per type
+    o.items[0, 2 * 3] = np.nan          # a food's x
+    o.items[1, 2 * 8 + 1] = np.nan      # a poison's y
+    if n > 3:
+        o.items[3, 2 * 15] = np.nan; o.items[3, 1] = np.nan   # one of each
+    observe(o, sides, 'observe')
+    bad_food, bad_poison = np.isnan(o.items[:, :16]).any(1), np.isnan(o.items[:, 16:32]).any(1)
+    assert np.array_equal(np.isnan(o.obs[:, nb:nb + m]).all(1), bad_food) and np.array_equal(np.isnan(o.obs[:, nb:nb + m]).any(1), bad_food)
+    assert np.array_equal(np.isnan(o.obs[:, nb + m:]).all(1), bad_poison) and np.array_equal(np.isnan(o.obs[:, nb + m:]).any(1), bad_poison)
+    step(o, sides, np.zeros((n, o.ad), F) + F(0.1), 'step')
+    assert np.array_equal(o.done.astype(bool), bad_food | bad_poison)
+    covered(need, nan_types=int(bad_food.sum() + bad_poison.sum()), clean=int((~bad_food & ~bad_poison).sum()))
+
+
+def orientation32(p, q, r):
+    val = F(F(q[1] - p[1]) * F(r[0] - q[0])) - F(F(q[0] - p[0]) * F(r[1] - q[1]))
+    return 1 if val > 0 else (2 if val < 0 else 0)
+
+
+def on_segment32(p, q, r):
+    # (fmaxf / fminf: a NaN operand is ignored)
+    return bool(q[0] <= np.fmax(p[0], r[0]) and q[0] >= np.fmin(p[0], r[0]) and q[1] <= np.fmax(p[1], r[1]) and q[1] >= np.fmin(p[1], r[1]))
+
+
+def collinear_verdict(robot, target, wall):
+    """intersection_utils.py:14-71 on fp32 values: which rule decides -- 'cross', 'p2', 'q2', 'p1', 'q1' (a collinear end point lying on the other
+    segment), 'collinear_apart' (some orientation is 0 and no rule fires) or None (apart, no zero)"""
+    p1, q1, p2, q2 = robot, target, wall[0:2], wall[2:4]
+    o1, o2, o3, o4 = orientation32(p1, q1, p2), orientation32(p1, q1, q2), orientation32(p2, q2, p1), orientation32(p2, q2, q1)
+    if o1 != o2 and o3 != o4:
+        return 'cross'
+    for name, zero, on in (('p2', o1, (p1, p2, q1)), ('q2', o2, (p1, q2, q1)), ('p1', o3, (p2, p1, q2)), ('q1', o4, (p2, q1, q2))):
+        if zero == 0 and on_segment32(*on):
+            return name
+    return 'collinear_apart' if 0 in (o1, o2, o3, o4) else None
+
+
+BOX_LINES = np.array([[1, 2, 1, -2], [-5, -2, -5, 2], [-5, -2, 1, -2]], F)   # the maze box's three lines (maze_scene.py:15-21)
+# (robot, target): robots standing exactly on the line of an axis-aligned wall, targets on it too
+COLLINEAR = [((1, 3), (1, 5)),       # beyond the wall's end, looking away: every orientation 0, nothing between -> the target is seen
+             ((1, 3), (1, 0)),       # the wall's first end point lies between robot and target
+             ((1, -3), (1, 0)),      # its second end point does
+             ((1, 0), (1, 1)),       # the robot itself stands on the wall, no end point between
+             ((-4, -2), (-3, -2))]   # on the horizontal wall; the two vertical ones have one collinear end point each, off the segment
+
+
+def collinear_segments(make, n, need):
+    """AntMaze with sense_target (ant_maze_bullet_env.py:135-178): the target is hidden when the segment robot -> target meets one of the box's lines;
+    the collinear rules of intersection_utils.py decide here, on exact zeros.  The sensor range is wide so that the distance never hides the target."""
+    targets = [t for _, t in COLLINEAR]
+    o, sides = start(make, K.HRL_ANT_MAZE, num_envs=n, seed=3, auto_reset=0, sense_target=1, n_bins=8, sensor_range=30.0, targets=targets)
+    o.state[:, 0:2] = np.array([r for r, _ in COLLINEAR], F)[:n]
+    o.state[:, 3:7] = [0, 0, 0, 1]; at_rest(o, 0.75)
+    o.aux[:, 3] = np.arange(n)
+    seen = collections.Counter()
+    hidden = np.zeros(n, bool)
+    for i in range(n):
+        for wall in BOX_LINES:   # the kernel stops at the first line that hides the target
+            v = collinear_verdict(o.state[i, 0:2], np.array(targets[i], F), wall)
+            seen[v or 'apart'] += 1
+            if v not in (None, 'collinear_apart'):
+                hidden[i] = True
+                break
+    observe(o, sides, 'observe')
+    assert np.array_equal((o.obs[:, 26:34] > 0).any(1), ~hidden), (o.obs[:, 26:34], hidden)   # a seen target lights one bin
+    step(o, sides, np.zeros((n, 8), F) + F(0.1), 'step')
+    covered(need, **seen)
+
+
+def target_index_outside_the_table(make, kind, n):
+    """maze kinds: aux[3] is the caller's; an index outside the constructor's table -- HRL_MAX_TARGETS, a large value, negative ones -- reads entry 0:
+    the same observation and step as a twin whose aux[3] IS 0"""
+    o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=0, inner_rew_weight=1.0)
+    twin = orc.OracleEnv(orc.default_config(kind, num_envs=n, seed=3, auto_reset=0, inner_rew_weight=1.0), np.float32)
+    twin.reset()
+    outside = np.array([K.HRL_MAX_TARGETS, 1 << 20, -1, -2 ** 31, 2], np.int32)[:n]   # the last one: inside, the control
+    o.aux[:, 3] = outside
+    twin.aux[:, 3] = np.where((outside >= 0) & (outside < K.HRL_MAX_TARGETS), outside, 0)
+    for env in (o, twin):
+        env.state[:, 0:2] = [3.0, 1.0]
+    observe(o, sides, 'observe'); twin.observe()
+    assert np.array_equal(o.obs, twin.obs)
+    a = uniform(np.random.RandomState(1), n, 8, 0.5)
+    step(o, sides, a, 'step'); twin.step(a)
+    assert np.array_equal(o.obs, twin.obs) and np.array_equal(o.rew, twin.rew) and np.array_equal(o.state, twin.state)
+    assert np.array_equal(o.aux[:, 3], outside)   # the caller's value is left as it is
+    covered(dict(outside=4), outside=int((twin.aux[:, 3] != outside).sum()))
+
+
+def time_limit_on_the_terminal_step(make, kind, n, auto_reset):
+    """gym TimeLimit: `truncated` = ended by the step limit ALONE.  max_episode_steps = 3 is reached on the very step on which envs 0 and 1 end
+    on their own (a NaN velocity ends any kind's episode): done, not truncated, the terminal observation in final_obs; the others are truncated."""
+    o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=auto_reset, max_episode_steps=3)
+    o.final_obs[...] = -7.0
+    for s in sides:
+        s.fill('final_obs', -7.0)
+    rng = np.random.RandomState(6)
+    for t in range(3):
+        if t == 2:
+            o.state[0:2, 15] = np.nan
+        step(o, sides, uniform(rng, n, o.ad, 0.3), t)
+        assert np.all(o.done == (t == 2)) and not (t < 2 and o.truncated.any())
+    both = np.arange(n) < 2
+    assert np.array_equal(o.truncated.astype(bool), ~both) and np.all(o.info[:, 3] == 3)
+    assert np.isnan(o.final_obs[both]).any(1).all() and np.isfinite(o.final_obs[~both]).all()
+    assert np.array_equal(o.aux[:, 0], np.zeros(n) if auto_reset else np.full(n, 3)) and (np.isfinite(o.obs).all() if auto_reset else True)
+    covered(dict(both=2, alone=1), both=int(both.sum()), alone=int((~both).sum()))
+
+
+def null_items(make, kind, n):
+    """The kinds that keep nothing in the items record may hand the step NULL for it (include/hrl_envs.h): resets and steps -- through the time
+    limit's in-step reset -- without the record, with it, and without it again; with it, it stays all zeros"""
+    o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=1, max_episode_steps=3)
+    rng = np.random.RandomState(7)
+    for given in (False, True, False):
+        for s in sides:
+            s.give_items(given)
+            s.reset()
+        o.reset()
+        check(o, sides, ('reset', given))
+        for t in range(4):
+            step(o, sides, uniform(rng, n, o.ad), (given, t))
+    assert not o.items.any() and o.aux[:, 2].min() >= 2
+
+
+def sixty_four_redraws(make, kind, n, need):
+    """The rejection loops that place things draw at most 64 times and keep the last draw.  Gather kinds: robot_object_spacing = 100 m refuses every
+    place of the 14 m world, so every pickup's respawn runs out of draws (gather_scene.py:52-62).  AntFlagrun with goals near the robot
+    (ant_flagrun_env.py:80-89): a robot 50 m outside the arena has no goal within 1.5 m that lies inside it."""
+    rng = np.random.RandomState(5)
+    if kind in GATHER:
+        o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=0, robot_object_spacing=100.0)
+        picked = 0
+        for t in range(2):
+            o.state[:, 0:2] = o.items.reshape(n, 16, 2)[np.arange(n), (np.arange(n) + 5 * t) % 16] + np.float32(0.25)
+            before = o.items.copy()
+            step(o, sides, uniform(rng, n, o.ad, 0.3), t)
+            moved = np.any((o.items != before).reshape(n, 16, 2), axis=2)
+            picked += int(moved.sum())
+            assert np.all(np.abs(o.items[moved.repeat(2, axis=1)]) <= 7.0)   # the 64th draw is kept, refused or not: inside the world
+        covered(need, exhausted=picked)
+    else:
+        o, sides = start(make, kind, num_envs=n, seed=3, auto_reset=0, flag_max_targets=0, flag_max_target_dist=3.0, flag_timeout=2,
+                         flag_enclosed=0, centroid_n_static=1, centroid_static_sum=(0.0, 0.0))
+        o.state[:, 0:2] = [50.0, -50.0]
+        outside = 0
+        for t in range(4):
+            before = o.items[:, 0:2].copy()
+            step(o, sides, uniform(rng, n, o.ad, 0.3), t)
+            new = np.any(o.items[:, 0:2] != before, axis=1)
+            outside += int((new & (np.abs(o.items[:, 0:2]) >= 5.0).any(1)).sum())   # a goal outside the arena: only the 64th draw is kept unseen
+        covered(need, exhausted=outside)
+
+
+
+def segment_distance(p1, q1, p2, q2):
+    """distance of two segments in fp64 (Ericson, Real-Time Collision Detection 5.1.9)"""
+    d1, d2, r = q1 - p1, q2 - p2, p1 - p2
+    a, e, f, c, b = d1 @ d1, d2 @ d2, d2 @ r, d1 @ r, d1 @ d2
+    den = a * e - b * b
+    s = np.clip((b * f - c * e) / den, 0, 1) if den > 1e-12 else 0.0
+    t = (b * s + f) / e
+    if t < 0:
+        t, s = 0.0, np.clip(-c / a, 0, 1)
+    elif t > 1:
+        t, s = 1.0, np.clip((b - c) / a, 0, 1)
+    return float(np.linalg.norm((p1 + d1 * s) - (p2 + d2 * t)))
+
+
+# (joint angles) of poses in which two capsules of opposite legs CROSS: legs 0 and 2 (1 and 3) are images of each other under the half turn about
+# the torso's vertical axis, so with (hip, ankle) against (-hip, -ankle) their axes meet on that axis.  Found by a search over such poses for
+# those where the two closest points come out bit-identical in fp32 (most come out a rounding apart); fp32 values, written exactly
+CROSSING_AXES = [
+    [3.0, float.fromhex('-0x1.a34acap-1'), 0, 0, -3.0, float.fromhex('0x1.a34acap-1'), 0, 0],
+    [2.5, float.fromhex('-0x1.22a428p-3'), 0, 0, -2.5, float.fromhex('0x1.22a428p-3'), 0, 0],
+    [0, 0, float.fromhex('0x1.162382p+1'), float.fromhex('0x1.472a74p-4'), 0, 0, float.fromhex('-0x1.162382p+1'), float.fromhex('-0x1.472a74p-4')],
+    [-2.75, float.fromhex('0x1.aeb054p-1'), 0, 0, 2.75, float.fromhex('-0x1.aeb054p-1'), 0, 0],
+    [2.875, float.fromhex('0x1.87b818p-3'), 0, 0, -2.875, float.fromhex('-0x1.87b818p-3'), 0, 0],
+]
+
+
+def crossing_capsule_axes(make, n, need):
+    """Self collision with the axes of two capsules INTERSECTING: the closest points coincide, their distance is 0 and there is no direction to
+    normalise -- the contact keeps its default normal (0, 0, 1) and a depth of both radii.  Hips teleported far out of their range, torsos level
+    and high above the ground.  Counted on the oracle's side: the oracle sees self contacts, and in fp64 kinematics of the fp32 pose two axes of
+    the two legs pass within 1e-6 m of each other (that the fp32 distance is exactly 0 is what the poses were picked for; nothing on the
+    oracle's side reports it)."""
+    o, sides = start(make, K.HRL_ANT_FLAT, num_envs=n, seed=5, auto_reset=0)
+    o.state[:, 0:2] = 0; o.state[:, 3:7] = [0, 0, 0, 1]; at_rest(o, 3.0)
+    o.state[:, 7:15] = np.array(CROSSING_AXES, F)[:n]
+    self_contacts = crossing = 0
+    for i in range(n):
+        q = o.state[i, :15].astype(np.float64); info = np.zeros(3, np.int32); dbg = np.zeros(13, np.int32)
+        orc.lib().orc_ant_substeps_items_f64(C.byref(o.cfg), orc.ptr(q.copy()), orc.ptr(np.zeros(14)), orc.ptr(np.zeros(8)), 1, None, 0, orc.ptr(info), orc.ptr(dbg), None)
+        self_contacts += int((dbg[1:] >= 64).any())
+        pts = cc.leg_points(o.cfg.model, q)
+        legs = [l for l in range(4) if o.state[i, 7 + 2 * l] != 0]
+        segs = [[(q[:3], pts[l, 0]), (pts[l, 0], pts[l, 1]), (pts[l, 1], pts[l, 2])] for l in legs]
+        crossing += int(min(segment_distance(a0, a1, b0, b1) for k, (a0, a1) in enumerate(segs[0]) for m, (b0, b1) in enumerate(segs[1]) if k or m) < 1e-6)
+    observe(o, sides, 'observe')
+    step(o, sides, np.zeros((n, 8), F), 'step')
+    covered(need, self_contacts=self_contacts, crossing=crossing)
+
+
+# (seed, episode, goal index) of AntFlagrun goals of the shared list whose 64 draws are ALL refused at flag_size = 1.0001 (a draw is refused within
+# 0.5 m of the origin: with the smallest legal arena that is 79 % of them, 64 in a row 2e-7 of all goals) -- found by a search over episodes
+EXHAUSTED_GOALS = (7, [(123491, 28), (257309, 39)])
+
+
+def exhausted_goal_draws(make, n):
+    """flag_goal (ant_flagrun_env.py:71-78) draws at most 64 times and keeps the last draw: episodes and goal indexes at which that happens, written
+    into aux[2] / aux[3] of envs 0 and 1 -- their goal lies within 0.5 m of the origin, which no accepted draw does; the others are the control"""
+    seed, hits = EXHAUSTED_GOALS
+    o, sides = start(make, K.HRL_ANT_FLAGRUN, num_envs=n, seed=seed, auto_reset=0, flag_size=1.0001)
+    for i, (ep, k) in enumerate(hits):
+        o.aux[i, 2] = ep; o.aux[i, 3] = k
+    g = np.zeros((n, 2), F)
+    for i in range(n):
+        orc.lib().orc_flag_goal_f32(C.byref(o.cfg), int(o.aux[i, 2]), int(o.aux[i, 3] & 0xffff), orc.ptr(g[i:i + 1]))
+    kept = np.sqrt((g.astype(np.float64) ** 2).sum(1)) < 0.5
+    observe(o, sides, 'observe')
+    step(o, sides, uniform(np.random.RandomState(1), n, 8, 0.3), 'step')
+    covered(dict(exhausted=len(hits), accepted=1), exhausted=int(kept.sum()), accepted=int((~kept).sum()))
+
+
+def nan_robot_with_the_target_on_a_wall(make, n, need):
+    """The fourth collinear rule of intersection_utils.py (the TARGET lies on the wall's segment) decides only where the robot's place is NaN: every
+    orientation that involves it is then 0 -- neither > 0 nor < 0 --, the rules that ask whether something lies between a NaN and the target find
+    nothing, and the target on the wall is what is left.  (With a finite robot the rule cannot decide against the box's axis-aligned walls: see
+    tests/STEP_COVERAGE.md, line 1881.)  A NaN distance does not hide the target either: `dist > range` is false."""
+    targets = [(1.0, 0.0), (-5.0, 1.0), (-2.0, -2.0), (1.0, 1.0), (3.0, 0.0)]
+    o, sides = start(make, K.HRL_ANT_MAZE, num_envs=n, seed=3, auto_reset=0, sense_target=1, n_bins=8, sensor_range=30.0, targets=targets)
+    o.state[:, 0:2] = [3.0, 0.5]; o.state[:, 3:7] = [0, 0, 0, 1]; at_rest(o, 0.75)
+    o.state[:4, 0] = np.nan   # env 4: the control, a finite robot and a target in the open
+    o.aux[:, 3] = np.arange(n)
+    seen = collections.Counter()
+    for i in range(n):
+        for wall in BOX_LINES:
+            v = collinear_verdict(o.state[i, 0:2], np.array(targets[i], F), wall)
+            seen[v or 'apart'] += 1
+            if v not in (None, 'collinear_apart'):
+                break
+    observe(o, sides, 'observe')
+    step(o, sides, np.zeros((n, 8), F) + F(0.1), 'step')
+    covered(need, **seen)

@@ -31,3 +31,8 @@ def test_observe_writes_nothing_but_the_observation():
         for k in ('state', 'items', 'aux', 'rew', 'done', 'info'):
             assert np.array_equal(getattr(e, k), before[k], equal_nan=True), (kind, k)
         assert np.array_equal(e.obs[3], before['obs'][3], equal_nan=True) and not np.array_equal(e.obs[0], before['obs'][0])
+
+
+def test_observation_edges_on_the_wave_phases():
+    """tests/golden/obs_edges.json: the angle fold, the bin edges, the collinear segment rules and the gimbal-lock property, zero readings excused"""
+    golden_replay.check_edges(golden_replay.replay_edges(Emu, orc.default_config))

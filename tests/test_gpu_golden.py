@@ -49,3 +49,9 @@ def test_set_state_returns_the_observation_of_the_new_state():
         obs2 = g.observe(mask).cpu().numpy(); o.observe(mask.numpy())
         assert np.array_equal(obs2, o.obs, equal_nan=True) and np.array_equal(obs2[3], obs[3], equal_nan=True)
         g.close()
+
+
+def test_observation_edges_on_the_device():
+    """tests/golden/obs_edges.json: the angle fold, the bin edges, the collinear segment rules and the gimbal-lock property, zero readings excused"""
+    from hrl_pybullet_envs_amd import _lib
+    golden_replay.check_edges(golden_replay.replay_edges(Device, _lib.default_config))

@@ -497,3 +497,63 @@ def test_device_reproduces_the_committed_specification_fingerprint():
     want = json.load(open(S.PATH))
     got = S.fingerprint(Device)
     assert got == want, [k for k in want if got.get(k) != want[k]]
+
+
+# ------------------------------------------------------------------ directed scenarios for branches no rollout enters (tests/STEP_COVERAGE.md)
+ANT_N, POINT_N = 5, 3   # one group of four plus a ragged one; the point bot
+
+
+@pytest.mark.parametrize('kind', [K.HRL_ANT_FLAT, K.HRL_ANT_GATHER, K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ, K.HRL_ANT_FLAGRUN, K.HRL_POINT_GATHER])
+def test_gimbal_lock(kind):
+    point = kind == K.HRL_POINT_GATHER
+    P.gimbal_lock(make, kind, POINT_N if point else ANT_N, need=dict(exact=3, band=3, control=3) if point else dict(exact=6, band=6, control=3))
+
+
+@pytest.mark.parametrize('kind', [K.HRL_ANT_GATHER, K.HRL_POINT_GATHER, K.HRL_ANT_MAZE])
+def test_angle_wraps_and_bin_edges(kind):
+    P.angle_wraps_and_bin_edges(make, kind, POINT_N if kind == K.HRL_POINT_GATHER else ANT_N,
+                                need=dict(tiny_negative=2, two_pi_or_more=1, below_minus_pi=1, top_edge=1, last_bin=1, lit=4, last_bin_lit=1))
+
+
+@pytest.mark.parametrize('kind', [K.HRL_ANT_GATHER, K.HRL_POINT_GATHER])
+def test_nan_item_in_the_nearest_first_order(kind):
+    point = kind == K.HRL_POINT_GATHER
+    P.nan_item_in_the_nearest_first_order(make, kind, POINT_N if point else ANT_N, need=dict(nan_types=2 if point else 4, clean=1))
+
+
+def test_collinear_segments():
+    P.collinear_segments(make, ANT_N, need=dict(p2=1, q2=1, p1=2, collinear_apart=4, apart=1))
+
+
+@pytest.mark.parametrize('kind', [K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ])
+def test_target_index_outside_the_table(kind):
+    P.target_index_outside_the_table(make, kind, ANT_N)
+
+
+@pytest.mark.parametrize('auto_reset', [0, 1])
+@pytest.mark.parametrize('kind', KINDS)
+def test_time_limit_on_the_terminal_step(kind, auto_reset):
+    P.time_limit_on_the_terminal_step(make, kind, POINT_N if kind == K.HRL_POINT_GATHER else ANT_N, auto_reset)
+
+
+@pytest.mark.parametrize('kind', [K.HRL_ANT_FLAT, K.HRL_ANT_MAZE, K.HRL_ANT_MAZE_MJ])
+def test_null_items(kind):
+    P.null_items(make, kind, ANT_N)
+
+
+@pytest.mark.parametrize('kind', [K.HRL_ANT_GATHER, K.HRL_POINT_GATHER, K.HRL_ANT_FLAGRUN])
+def test_sixty_four_redraws(kind):
+    n = POINT_N if kind == K.HRL_POINT_GATHER else ANT_N
+    P.sixty_four_redraws(make, kind, n, need=dict(exhausted=n))
+
+
+def test_crossing_capsule_axes():
+    P.crossing_capsule_axes(make, ANT_N, need=dict(self_contacts=ANT_N, crossing=ANT_N))
+
+
+def test_exhausted_goal_draws():
+    P.exhausted_goal_draws(make, ANT_N)
+
+
+def test_nan_robot_with_the_target_on_a_wall():
+    P.nan_robot_with_the_target_on_a_wall(make, ANT_N, need=dict(q1=4, apart=3))

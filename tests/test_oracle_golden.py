@@ -605,3 +605,12 @@ def test_configs_beyond_the_default_sizes():
     check_maze_mj_step(g['maze_mj_step'])
     assert {len(c['food']) + len(c['poison']) for c in g['food_sensor']} == {32, 64}
     assert any(c['food_rew'] != 0 for c in g['gather_step']) and any(c['done'] for c in g['maze_step'])
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_observation_edges(dtype):
+    """tests/golden/obs_edges.json (the reference's get_sensor_readings and segment_intersection at the edges of the angle fold, of the bins and of the
+    collinear rules; the gimbal-lock property in place of the absent getEulerFromQuaternion) on the oracle in both formats: zero readings excused"""
+    import golden_replay
+    report = golden_replay.replay_edges(lambda cfg: golden_replay.OracleSide(cfg, dtype), orc.default_config, half_pi=dtype(math.pi / 2))
+    golden_replay.check_edges(report)
