@@ -4,8 +4,9 @@ hrl_pybullet_envs_amd/libhrl_render_hip.so (the batched renderer, include/hrl_re
 include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched navigation field, include/hrl_field.h),
 hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h), hrl_pybullet_envs_amd/libhrl_see_hip.so (the
 batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map, include/hrl_frontier.h),
-hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h) and
-hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h).
+hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h),
+hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h) and hrl_pybullet_envs_amd/libhrl_chase_hip.so
+(the batched chase camera, include/hrl_chase.h).
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -34,6 +35,8 @@ FRONTIER = ('frontier', 'libhrl_frontier_hip.so', 'frontier_hip.hip', 'frontier_
 CAMERA = ('camera', 'libhrl_camera_hip.so', 'camera_hip.hip', 'camera_core.h', 'hrl_camera.h')
 # The link states stand on no other sensor: the step's own kinematics (step_core.h, included) restated in a specification of their own.
 LINKS = ('links', 'libhrl_links_hip.so', 'links_hip.hip', 'links_core.h', 'hrl_links.h')
+# The chase camera stands on the first-person camera's chain (render, scan, camera) and on the link states' specification.
+CHASE = ('chase', 'libhrl_chase_hip.so', 'chase_hip.hip', 'chase_core.h', 'hrl_chase.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -137,8 +140,19 @@ def build_links(force=False, verbose=False):
     return lib
 
 
+def build_chase(force=False, verbose=False):
+    """The chase camera's library; returns its path.  It depends on everything the first-person camera and the link states depend on
+    plus its own three files."""
+    _, lib, source, core, header = CHASE
+    lib = os.path.join(PKG, lib)
+    sources = [source, core, CAMERA[3], LINKS[3], 'sensor_launch.h'] + [c for *_, c, _ in SENSORS[:2]] + SOURCES[1:]
+    if force or _stale(lib, sources, ['hrl_envs.h', header, CAMERA[4], LINKS[4]] + [h for *_, h in SENSORS[:2]]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The ten libraries; returns the step library's path."""
+    """The eleven libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
@@ -148,10 +162,11 @@ def build(force=False, verbose=False):
     build_frontier(force, verbose)
     build_camera(force, verbose)
     build_links(force, verbose)
+    build_chase(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE]:
         print(os.path.join(PKG, lib))

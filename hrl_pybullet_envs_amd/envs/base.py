@@ -250,6 +250,13 @@ class BatchedGymEnv:
         launch one body at a time."""
         return self._backend().links(spec, mask, out)
 
+    def chase_batch(self, spec=None, mask=None, out=None):
+        """The third-person image of EVERY env in one launch: Chase(depth float32 [N, H, W], seg int32 [N, H, W], rgb uint8 [N, H, W, 3]) on
+        the env's device: what a camera 3 m behind each robot and 30 degrees above it sees -- the robot's own body, link by link, on a
+        checkered ground, with the walls, the maze box, the items and the target (BatchedEnv.chase; chase_device.default_spec for other
+        sizes, angles, distances and classes).  The picture `render()` describes, for all envs and without leaving HBM."""
+        return self._backend().chase(spec, mask, out)
+
     def close(self):
         if self._env is not None:
             self._env.close()

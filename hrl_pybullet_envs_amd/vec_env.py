@@ -353,6 +353,25 @@ class BatchedEnv:
         self._sensor_launch('_last_links_mask', mask, lambda m, stream: Lk.links(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
+    def chase(self, spec=None, mask=None, out=None):
+        """The third-person image of every env, the robot's body in it: a namedtuple Chase(depth float32 [N, H, W], seg int32 [N, H, W], rgb
+        uint8 [N, H, W, 3]) on this device, from ONE launch on the current stream (chase_device.py, include/hrl_chase.h).  A pinhole
+        camera orbits each robot at spec.distance, yaw and pitch and looks at it: it sees the walls, the maze box, the item cubes, the
+        target post and a checkered ground as solids, the ant as its torso sphere and twelve capsules (the point bot as its cube): depth =
+        metres along the optical axis (spec.max_range where nothing was hit), seg = class | index << 8 | face << 16 with class
+        chase_device.HIT_ROBOT and index = the link for the body (chase_device.decode), rgb = the class or link colour shaded by face,
+        the sky where nothing was hit.  `spec`: an hrl_chase_spec (chase_device.default_spec(cfg, frame, width, height, yaw_degrees,
+        pitch_degrees, distance, hfov_degrees, vfov_degrees, target, target_height, max_range, classes, tile)); None = 64 x 48 pixels from
+        3 m behind the torso and 30 degrees above it, turning with the heading.  Envs with mask[i] == 0 keep what `out` holds (zeros in
+        fresh tensors).  `out`: a Chase of tensors to reuse; a None member is not computed.  The image is of the state / items / aux
+        tensors as they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import chase_device as Ch
+        if spec is None:
+            spec = self._default_spec('chase', lambda: Ch.default_spec(self.cfg))
+        out = self._fresh_out(Ch, Ch.Chase, Ch.shapes(spec), spec, mask) if out is None else Ch.check_out(out, self.num_envs, spec, self.device)
+        self._sensor_launch('_last_chase_mask', mask, lambda m, stream: Ch.chase(self.cfg, self._bufs_ref, spec, m, out, stream))
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
