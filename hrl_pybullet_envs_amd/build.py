@@ -5,8 +5,9 @@ include/hrl_probe.h), hrl_pybullet_envs_amd/libhrl_field_hip.so (the batched nav
 hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route.h), hrl_pybullet_envs_amd/libhrl_see_hip.so (the
 batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map, include/hrl_frontier.h),
 hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h),
-hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h) and hrl_pybullet_envs_amd/libhrl_chase_hip.so
-(the batched chase camera, include/hrl_chase.h).
+hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h), hrl_pybullet_envs_amd/libhrl_chase_hip.so
+(the batched chase camera, include/hrl_chase.h) and hrl_pybullet_envs_amd/libhrl_dyn_hip.so (the batched dynamics terms,
+include/hrl_dyn.h): twelve libraries.
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -37,6 +38,8 @@ CAMERA = ('camera', 'libhrl_camera_hip.so', 'camera_hip.hip', 'camera_core.h', '
 LINKS = ('links', 'libhrl_links_hip.so', 'links_hip.hip', 'links_core.h', 'hrl_links.h')
 # The chase camera stands on the first-person camera's chain (render, scan, camera) and on the link states' specification.
 CHASE = ('chase', 'libhrl_chase_hip.so', 'chase_hip.hip', 'chase_core.h', 'hrl_chase.h')
+# The dynamics terms stand on the link states' specification (the sites) and, like it, on the step's own model (step_core.h, included).
+DYN = ('dyn', 'libhrl_dyn_hip.so', 'dyn_hip.hip', 'dyn_core.h', 'hrl_dyn.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -151,8 +154,18 @@ def build_chase(force=False, verbose=False):
     return lib
 
 
+def build_dyn(force=False, verbose=False):
+    """The dynamics terms' library; returns its path.  It depends on everything the link states depend on, on their specification and
+    header, and on its own three files."""
+    _, lib, source, core, header = DYN
+    lib = os.path.join(PKG, lib)
+    if force or _stale(lib, [source, core, LINKS[3], 'sensor_launch.h'] + SOURCES[1:], ['hrl_envs.h', header, LINKS[4]]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The eleven libraries; returns the step library's path."""
+    """The twelve libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
@@ -163,10 +176,11 @@ def build(force=False, verbose=False):
     build_camera(force, verbose)
     build_links(force, verbose)
     build_chase(force, verbose)
+    build_dyn(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE, DYN]:
         print(os.path.join(PKG, lib))

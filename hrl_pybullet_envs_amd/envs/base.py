@@ -250,6 +250,14 @@ class BatchedGymEnv:
         launch one body at a time."""
         return self._backend().links(spec, mask, out)
 
+    def dynamics_batch(self, spec=None, tau=None, mask=None, out=None):
+        """The dynamics terms of EVERY env in one launch: Dynamics(mass [N, nv, nv], bias, accel [N, nv], jac [N, S, 3, nv], com [N, 3],
+        momentum [N, 6], energy [N, 2]) on the env's device, in the order of the state's qvel (nv = 14, the point bot 6): the mass
+        matrix, the bias force, the contact-free acceleration under `tau`, the Jacobians of the spec's sites -- by default the four foot
+        tips -- and the whole body's centre of mass, momenta and energies (BatchedEnv.dynamics; dyn_device.default_spec for other
+        sites, dyn_device.torques for the `tau` of an action)."""
+        return self._backend().dynamics(spec, tau, mask, out)
+
     def chase_batch(self, spec=None, mask=None, out=None):
         """The third-person image of EVERY env in one launch: Chase(depth float32 [N, H, W], seg int32 [N, H, W], rgb uint8 [N, H, W, 3]) on
         the env's device: what a camera 3 m behind each robot and 30 degrees above it sees -- the robot's own body, link by link, on a

@@ -353,6 +353,30 @@ class BatchedEnv:
         self._sensor_launch('_last_links_mask', mask, lambda m, stream: Lk.links(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
+    def dynamics(self, spec=None, tau=None, mask=None, out=None):
+        """The dynamics terms of every env's robot: a namedtuple Dynamics(mass, bias, accel, jac, com, momentum, energy) on this device,
+        from ONE launch on the current stream (dyn_device.py, include/hrl_dyn.h) -- what the simulator's calculateMassMatrix,
+        calculateInverseDynamics and calculateJacobian answer one env at a time.  Generalised velocities are the state's qvel in its own
+        order, (v of the torso's origin, omega, joint rates): nv = 14 for the ants, 6 for the point bot.  mass [N, nv, nv] = the
+        joint-space mass matrix M(q) (bitwise symmetric); bias [N, nv] = Coriolis and centrifugal terms, gravity and the model's damping,
+        so that M udot + bias = tau describes the contact-free robot; accel [N, nv] = M^-1 (tau - bias); jac [N, S, 3, nv] = the linear
+        Jacobian of the spec's sites, points fixed to links (by default the four foot tips): jac @ qvel is the site's velocity; com
+        [N, 3] = the whole-body centre of mass; momentum [N, 6] = linear momentum and angular momentum about the centre of mass; energy
+        [N, 2] = kinetic and potential energy.  `spec`: an hrl_dyn_spec (dyn_device.default_spec(cfg, sites)); None = the default sites.
+        `tau`: float32 [N, nv] on this device, the applied generalised force of `accel` (dyn_device.torques(cfg, actions)); None =
+        zeros.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh tensors).  `out`: a Dynamics of tensors to reuse; a None
+        member is not computed.  The terms are of the state tensor as it is; nothing else is read or written.  Capturable: call it once
+        before the capture."""
+        from . import dyn_device as Dy
+        if spec is None:
+            spec = self._default_spec('dynamics', lambda: Dy.default_spec(self.cfg))
+        if tau is not None:
+            Dy.check_tau(tau, self.num_envs, self.cfg, self.device)
+        out = self._fresh_out(Dy, Dy.Dynamics, Dy.shapes(self.cfg, spec), spec, mask) if out is None else Dy.check_out(out, self.num_envs, self.cfg, spec, self.device, tau)
+        self._sensor_launch('_last_dynamics_mask', mask, lambda m, stream: Dy.dynamics(self.cfg, self._bufs_ref, spec, None if tau is None else tau.data_ptr(), m, out, stream))
+        self._last_dynamics_tau = tau  # until the stream has consumed it
+        return out
+
     def chase(self, spec=None, mask=None, out=None):
         """The third-person image of every env, the robot's body in it: a namedtuple Chase(depth float32 [N, H, W], seg int32 [N, H, W], rgb
         uint8 [N, H, W, 3]) on this device, from ONE launch on the current stream (chase_device.py, include/hrl_chase.h).  A pinhole

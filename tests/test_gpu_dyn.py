@@ -1,0 +1,241 @@
+"""The batched dynamics terms on the MI355X (csrc/dyn_hip.hip, include/hrl_dyn.h) against the host build of their specification
+(tests/dyn_host, csrc/dyn_core.h), bit for bit in all seven outputs, and their surface: tau, None members, masks, streams, `out=`, the gym
+classes' dynamics_batch(), and that the step does not notice them.  At most 1029 envs per test."""
+import numpy as np
+import pytest
+import torch
+
+import dyn_cases as dc
+import links_cases as lc
+from hrl_pybullet_envs_amd import _capi as K
+from hrl_pybullet_envs_amd import dyn_device as Dy
+from test_gpu_render import make_env, put, stepped   # the envs of 5 after reset + 30 steps: made once, shared with the renderer's tests
+
+pytestmark = pytest.mark.gpu
+N = 5
+SIZES = (1, 5, 37, 1029)   # a lone env | a part of a group | two full groups and a tail of 5 | 64 groups and a tail of 5
+
+
+def host_of(d):
+    return dc.Dynamics(*(x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in d))
+
+
+def same(a, b, nan_ok=False):
+    """Every member the same bits."""
+    return dc.same(host_of(a), host_of(b), nan_ok)
+
+
+def site_sets(kind):
+    """0 sites, the library's default ones (4; the point bot: 1) and 16 over every link."""
+    b = 1 if kind == K.HRL_POINT_GATHER else 13
+    return ((), lc.foot_sites() if b > 1 else ((0, (0.0, 0.0, 0.0)),), lc.sixteen_sites(b))
+
+
+def states_of(n, seed=0):
+    """n hand-made ant states: tilted torsos, joints at and between their stops, x and y out to +-10 m, velocities of the shards' scale."""
+    return np.concatenate([dc.hand_made(seed + k, 12) for k in range((n + 11) // 12)])[:n]
+
+
+def both(env, st, spec, tau=None, mask=None):
+    """(device terms, host-build terms) of the state records st, written into the env's tensor first."""
+    env.state.copy_(torch.from_numpy(np.array(st)))
+    t = None if tau is None else torch.from_numpy(tau).cuda()
+    return env.dynamics(spec, tau=t, mask=mask), dc.dyn_host(env.cfg, st, spec, tau=tau, mask=None if mask is None else mask.cpu().numpy())
+
+
+@pytest.mark.parametrize('kind', dc.KINDS)
+def test_device_equals_the_host_build_bit_for_bit(kind):
+    """The six default configurations x 0, 4 (1) and 16 sites x with and without tau at N = 5, on the states of 30 steps and (the ants) on
+    hand-made poses: mass, bias, accel, jac, com, momentum and energy equal the host build of dyn_core.h as uint32.  Then a NaN in another
+    place of every env's record: the same, a NaN for a NaN."""
+    env, st, it, aux = stepped(kind)
+    nv = Dy.nv(env.cfg)
+    try:
+        for s in (st,) + ((states_of(N, 20),) if nv == 14 else ()):
+            for sites in site_sets(kind):
+                for tau in (None, dc.taus(env.cfg, N, 1 + len(sites))):
+                    dev, host = both(env, s, dc.spec_of(sites), tau)
+                    assert tuple(dev.mass.shape) == (N, nv, nv) and tuple(dev.accel.shape) == (N, nv) and dev.com.dtype == torch.float32
+                    assert (dev.jac is None) == (not sites) and (not sites or tuple(dev.jac.shape) == (N, len(sites), 3, nv))
+                    assert same(dev, host), (kind, len(sites), tau is None)
+        assert same(env.dynamics(), dc.dyn_host(env.cfg, s, Dy.default_spec(env.cfg))), (kind, 'default')
+        bad = np.array(st)
+        for e, place in enumerate((0, 4, 9, 16, 24)):
+            bad[e, place] = np.nan
+        dev, host = both(env, bad, dc.spec_of(site_sets(kind)[2]), dc.taus(env.cfg, N))
+        assert same(dev, host, nan_ok=True) and not bool(torch.isfinite(dev.bias[3]).all())   # (env 3: a NaN velocity)
+    finally:
+        put(env, st, it, aux)
+
+
+@pytest.mark.parametrize('name', [n for n in dc.MODELS if n != 'defaults'])
+def test_device_equals_the_host_build_on_the_model_matrix(name):
+    """Every entry of dyn_cases.MODELS -- what the terms read of the model: the bodies' damping, the joints' damping and armature, the
+    density, gravity -- on an ant and on the point bot at N = 5, with tau and 16 sites."""
+    over = {'model_' + k: v for k, v in dc.MODELS[name].items()}
+    for kind in (K.HRL_ANT_MAZE, K.HRL_POINT_GATHER):
+        env = make_env(kind, N, **over)
+        env.reset()
+        st = states_of(N, 30)
+        st[:, 29:32] = env.state[:, 29:32].cpu().numpy()
+        dev, host = both(env, st, dc.spec_of(site_sets(kind)[2]), dc.taus(env.cfg, N))
+        assert same(dev, host), (name, kind)
+        env.close()
+
+
+@pytest.mark.parametrize('n', SIZES)
+def test_batch_sizes_masks_and_single_outputs(n):
+    """N = 1, 5, 37 and 1029 ant envs with tau and 16 sites: every output equals the host build; `mass` alone and `accel` alone (the
+    others NULL) equal it too and nothing else is written; under a random mask, with the first env masked and with the whole last group
+    masked the masked envs keep the bytes the tensors were filled with."""
+    env = make_env(K.HRL_ANT_GATHER, n)
+    env.reset()
+    st = states_of(n, 40 + n % 50)
+    st[:, 29:32] = env.state[:, 29:32].cpu().numpy()
+    spec = dc.spec_of(lc.sixteen_sites(13))
+    tau = dc.taus(env.cfg, n)
+    dev, host = both(env, st, spec, tau)
+    assert same(dev, host), n
+    t = torch.from_numpy(tau).cuda()
+    for name in ('mass', 'accel'):
+        filled = Dy.Dynamics(*(torch.full((n,) + shape, -3.0, device='cuda') for shape in Dy.shapes(env.cfg, spec)))
+        got = env.dynamics(spec, tau=t, out=Dy.Dynamics(**{name: getattr(filled, name)}))
+        assert all((x is None) == (k != name) for k, x in zip(dc.NAMES, got))
+        torch.cuda.synchronize()
+        assert np.array_equal(dc.bits(getattr(filled, name).cpu().numpy()), dc.bits(getattr(host, name))), (n, name)
+        assert all(bool((x == -3).all()) for k, x in zip(dc.NAMES, filled) if k != name), (n, name)
+    rng = np.random.RandomState(n)
+    last_group = np.arange(n) < (n - 1) // 16 * 16
+    masks = [rng.randint(0, 2, n), np.arange(n) != 0] + ([last_group] if n > 16 else [])
+    for m in masks:
+        mask = torch.from_numpy(np.asarray(m).astype(np.uint8) * 7)
+        out = Dy.Dynamics(*(torch.full((n,) + shape, -3.0, device='cuda') for shape in Dy.shapes(env.cfg, spec)))
+        assert env.dynamics(spec, tau=t, mask=mask, out=out) is out
+        o, on = host_of(out), np.asarray(m).astype(bool)
+        for x, y in zip(o, host):
+            assert np.array_equal(dc.bits(x[on]), dc.bits(y[on])) and (x[~on] == -3).all(), (n, m)
+    fresh = env.dynamics(spec, mask=torch.zeros(n, dtype=torch.uint8))
+    assert all(not bool(x.any()) for x in fresh)   # fresh tensors are zeros where the mask leaves envs unwritten
+    env.close()
+
+
+def test_dynamics_follow_the_stream():
+    """After step launches with nothing between them, on the env's stream and on a second stream, the terms are those of the state the
+    steps left, under the torques of the next action."""
+    kind, n = K.HRL_ANT_GATHER, 17
+    env = make_env(kind, n)
+    env.reset()
+    spec = dc.spec_of(lc.sixteen_sites(13))
+    acts = torch.rand(11, n, 8, device='cuda', generator=torch.Generator(device='cuda').manual_seed(6)) * 2 - 1
+    tau = Dy.torques(env.cfg, acts[10])
+    env.dynamics(spec)   # the constants are uploaded here
+    for t in range(10):
+        env.step(acts[t])
+    dev = env.dynamics(spec, tau=tau)
+    torch.cuda.synchronize()
+    assert same(dev, dc.dyn_host(env.cfg, env.state.cpu().numpy(), spec, tau=tau.cpu().numpy()))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for t in range(10):
+            env.step(acts[9 - t])
+        dev = env.dynamics(spec, tau=tau)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    assert same(dev, dc.dyn_host(env.cfg, env.state.cpu().numpy(), spec, tau=tau.cpu().numpy()))
+    env.close()
+
+
+def test_out_is_reused_and_checked():
+    env, st, it, aux = stepped(K.HRL_ANT_MAZE)
+    put(env, st, it, aux)
+    spec = dc.spec_of(lc.foot_sites())
+    out = Dy.Dynamics(*(torch.zeros((N,) + shape, device='cuda') for shape in Dy.shapes(env.cfg, spec)))
+    ptrs = [x.data_ptr() for x in out]
+    tau = torch.from_numpy(dc.taus(env.cfg, N)).cuda()
+    for r in range(2):   # the same tensors twice
+        got = env.dynamics(spec, tau=tau, out=out)
+        assert got is out and [x.data_ptr() for x in got] == ptrs
+        assert same(out, dc.dyn_host(env.cfg, st, spec, tau=tau.cpu().numpy())), r
+    alone = env.dynamics(spec, out=Dy.Dynamics(bias=torch.zeros(N, 14, device='cuda')))
+    assert isinstance(alone, Dy.Dynamics) and alone.mass is None and alone.jac is None and torch.equal(alone.bias, out.bias)
+    with pytest.raises(TypeError):
+        env.dynamics(spec, out=out._replace(com=out.com.double()))
+    with pytest.raises(TypeError):
+        env.dynamics(spec, out=tuple(out))
+    with pytest.raises(ValueError):
+        env.dynamics(spec, out=out._replace(mass=torch.zeros(N, 14, 13, device='cuda')))
+    with pytest.raises(ValueError):
+        env.dynamics(spec, out=out._replace(com=torch.zeros(N, 3)))   # on the host
+    with pytest.raises(ValueError):
+        env.dynamics(spec, out=Dy.Dynamics())
+    with pytest.raises(ValueError):
+        env.dynamics(spec, out=out._replace(accel=out.bias))   # aliased
+    with pytest.raises(ValueError):
+        env.dynamics(spec, tau=tau, out=out._replace(accel=tau))   # the input
+    with pytest.raises(ValueError):
+        env.dynamics(spec, tau=tau.cpu())
+    with pytest.raises(TypeError):
+        env.dynamics(spec, tau=tau.double())
+    bad = spec.copy()
+    bad.n_sites = 17
+    with pytest.raises(ValueError):
+        env.dynamics(bad)
+    from hrl_pybullet_envs_amd._lib import HrlError
+    bad = spec.copy()
+    bad.site_link[1] = 13
+    filled = Dy.Dynamics(*(torch.full((N,) + shape, -3.0, device='cuda') for shape in Dy.shapes(env.cfg, spec)))
+    with pytest.raises(HrlError) as e:
+        env.dynamics(bad, out=filled)
+    assert dc.dyn_host(env.cfg, st, bad, expect_ok=False)[1] in str(e.value)
+    torch.cuda.synchronize()
+    assert all(bool((x == -3).all()) for x in filled)
+
+
+def test_dynamics_batch_of_a_single_env_is_row_0_of_a_batch():
+    """The gym classes' dynamics_batch(): a batched env's equals its backend's dynamics() and the host build; a single env's [1, ...]
+    tensors hold the bits of row 0 of a batch made of the same state; the point bot has its six rows."""
+    import hrl_pybullet_envs_amd as H
+    env = H.AntMazeBulletEnv(num_envs=5, device='cuda:0', seed=3)
+    env.reset()
+    for _ in range(3):
+        env.step(torch.rand(5, 8, device='cuda') * 2 - 1)
+    b = env._backend()
+    tau = Dy.torques(b.cfg, torch.rand(5, 8, device='cuda') * 4 - 2)
+    t = env.dynamics_batch(tau=tau)
+    assert isinstance(t, Dy.Dynamics) and same(t, b.dynamics(tau=tau)) and same(t, dc.dyn_host(b.cfg, b.state.cpu().numpy(), Dy.default_spec(b.cfg), tau=tau.cpu().numpy()))
+    one = H.AntMazeBulletEnv(seed=4)
+    one.reset()
+    one.step(np.zeros(8))
+    ob = one._backend()
+    got = one.dynamics_batch(tau=tau[:1])
+    assert tuple(got.mass.shape) == (1, 14, 14) and tuple(got.jac.shape) == (1, 4, 3, 14)
+    b.state[0].copy_(ob.state[0])
+    row0 = b.dynamics(tau=tau)
+    assert same(got, Dy.Dynamics(*(x[:1] for x in row0)))
+    env.close()
+    one.close()
+    point = H.PointGatherBulletEnv(seed=5)
+    point.reset()
+    d = point.dynamics_batch()
+    assert tuple(d.mass.shape) == (1, 6, 6) and tuple(d.jac.shape) == (1, 1, 3, 6) and float(d.mass[0, 0, 0]) == 10.0
+    point.close()
+
+
+def test_the_step_does_not_notice_the_dynamics():
+    """10 steps of a 16-env gather shard with dynamics calls interleaved are bit-identical to the same steps without them."""
+    kind, n = K.HRL_ANT_GATHER, 16
+    a, b = make_env(kind, n), make_env(kind, n)
+    a.reset(); b.reset()
+    acts = torch.rand(10, n, 8, device='cuda', generator=torch.Generator(device='cuda').manual_seed(9)) * 2 - 1
+    specs = [dc.spec_of(s) for s in site_sets(kind)]
+    for t in range(10):
+        oa = [x.clone() for x in a.step(acts[t])[:3]]
+        b.dynamics(specs[t % 3], tau=Dy.torques(b.cfg, acts[t]))
+        ob = [x.clone() for x in b.step(acts[t])[:3]]
+        b.dynamics() if t % 2 else b.dynamics(specs[(t + 2) % 3], mask=torch.arange(n) % 2)
+        for x, y in zip(oa, ob):
+            assert torch.equal(x.view(torch.uint8), y.view(torch.uint8)), t
+    for name in ('state', 'items', 'aux'):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    a.close(); b.close()
