@@ -6,8 +6,8 @@ hrl_pybullet_envs_amd/libhrl_route_hip.so (the batched routes, include/hrl_route
 batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontier_hip.so (the batched frontier map, include/hrl_frontier.h),
 hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h),
 hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h), hrl_pybullet_envs_amd/libhrl_chase_hip.so
-(the batched chase camera, include/hrl_chase.h) and hrl_pybullet_envs_amd/libhrl_dyn_hip.so (the batched dynamics terms,
-include/hrl_dyn.h): twelve libraries.
+(the batched chase camera, include/hrl_chase.h), hrl_pybullet_envs_amd/libhrl_dyn_hip.so (the batched dynamics terms,
+include/hrl_dyn.h) and hrl_pybullet_envs_amd/libhrl_cast_hip.so (the batched ray test, include/hrl_cast.h): thirteen libraries.
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -40,6 +40,8 @@ LINKS = ('links', 'libhrl_links_hip.so', 'links_hip.hip', 'links_core.h', 'hrl_l
 CHASE = ('chase', 'libhrl_chase_hip.so', 'chase_hip.hip', 'chase_core.h', 'hrl_chase.h')
 # The dynamics terms stand on the link states' specification (the sites) and, like it, on the step's own model (step_core.h, included).
 DYN = ('dyn', 'libhrl_dyn_hip.so', 'dyn_hip.hip', 'dyn_core.h', 'hrl_dyn.h')
+# The ray test stands on the chase camera's whole chain (render, scan, camera, links, chase): its solids and their intersections.
+CAST = ('cast', 'libhrl_cast_hip.so', 'cast_hip.hip', 'cast_core.h', 'hrl_cast.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -164,8 +166,19 @@ def build_dyn(force=False, verbose=False):
     return lib
 
 
+def build_cast(force=False, verbose=False):
+    """The ray test's library; returns its path.  It depends on everything the chase camera depends on, on its specification and
+    header, and on its own three files."""
+    _, lib, source, core, header = CAST
+    lib = os.path.join(PKG, lib)
+    sources = [source, core, CHASE[3], CAMERA[3], LINKS[3], 'sensor_launch.h'] + [c for *_, c, _ in SENSORS[:2]] + SOURCES[1:]
+    if force or _stale(lib, sources, ['hrl_envs.h', header, CHASE[4], CAMERA[4], LINKS[4]] + [h for *_, h in SENSORS[:2]]):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The twelve libraries; returns the step library's path."""
+    """The thirteen libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
@@ -177,10 +190,11 @@ def build(force=False, verbose=False):
     build_links(force, verbose)
     build_chase(force, verbose)
     build_dyn(force, verbose)
+    build_cast(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE, DYN]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE, DYN, CAST]:
         print(os.path.join(PKG, lib))

@@ -265,6 +265,13 @@ class BatchedGymEnv:
         sizes, angles, distances and classes).  The picture `render()` describes, for all envs and without leaving HBM."""
         return self._backend().chase(spec, mask, out)
 
+    def cast_batch(self, rays, spec=None, mask=None, out=None, ray_link=None):
+        """The caller's 3-D rays against EVERY env's scene and robot in one launch: Cast(fraction float32 [N, R], seg int32 [N, R], point
+        and normal float32 [N, R, 3]) on the env's device -- the simulator's rayTestBatch(from, to) for all envs: `rays` [N, R, 6] holds
+        from and to per ray in the world, about the torso, in the heading's frame or in a link's body frame (BatchedEnv.cast;
+        cast_device.default_spec for the frame and the classes, cast_device.lidar_rays, down_rays and from_to for the rays)."""
+        return self._backend().cast(rays, spec, mask, out, ray_link)
+
     def close(self):
         if self._env is not None:
             self._env.close()

@@ -396,6 +396,41 @@ class BatchedEnv:
         self._sensor_launch('_last_chase_mask', mask, lambda m, stream: Ch.chase(self.cfg, self._bufs_ref, spec, m, out, stream))
         return out
 
+    def cast(self, rays, spec=None, mask=None, out=None, ray_link=None):
+        """The caller's 3-D rays against every env's scene and robot: a namedtuple Cast(fraction float32 [N, R], seg int32 [N, R], point
+        float32 [N, R, 3], normal float32 [N, R, 3]) on this device, from ONE launch on the current stream (cast_device.py,
+        include/hrl_cast.h) -- what the simulator's rayTestBatch(from, to) answers one env at a time.  `rays`: float32 [N, R, 6] on this
+        device, contiguous and 8-byte aligned, 1 <= R <= 1024: per ray `from` and `to` in the coordinates of spec.frame -- world
+        positions, offsets from the torso in world axes ('ego'), offsets turned by the heading ('heading': x forward, y left) or
+        coordinates in the body frame of a link ('link'; the link of ray r is ray_link[r], an int32 tensor [R] on this device shared by
+        all envs, None = the torso for every ray; a link out of range meets nothing).  A pattern [R, 6] is expanded to [N, R, 6] here,
+        which COPIES IT AT EVERY CALL: in a loop hand in cast_device.expand(pattern, N, device), materialised once.  The rays meet the
+        chase camera's solids under its rules: walls, the maze box, item cubes and the target post as prisms, the ground, the ant as its
+        torso sphere and twelve capsules (the point bot as its cube), entered from outside only; the nearest hit with 0 < t <= 1 wins.
+        fraction = t (1.0 where nothing was met), seg = class | index << 8 | face << 16 (cast_device.decode; class cast_device.HIT_ROBOT
+        with index = the link), point = the hit in world coordinates (`to` where nothing was met), normal = the outward unit normal in
+        world axes (zeros where nothing was met).  `spec`: an hrl_cast_spec (cast_device.default_spec(cfg, frame, n_rays, classes));
+        None = the 'heading' frame, every class, R rays.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh tensors).  `out`:
+        a Cast of tensors to reuse; a None member is not computed.  The answer is of the state / items / aux tensors as they are;
+        nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import cast_device as Ca
+        if isinstance(rays, torch.Tensor) and rays.dim() == 2:
+            rays = Ca.expand(rays, self.num_envs, self.device)
+        if spec is None:
+            r = int(rays.shape[1]) if isinstance(rays, torch.Tensor) and rays.dim() == 3 else 0
+            spec = self._default_spec(('cast', r), lambda: Ca.default_spec(self.cfg, n_rays=r))
+        why = Ca.size_error(spec)
+        if why is not None:
+            raise ValueError(why)
+        Ca.check_rays(rays, self.num_envs, spec, self.device)
+        if ray_link is not None:
+            Ca.check_ray_link(ray_link, spec, self.device)
+        out = self._fresh_out(Ca, Ca.Cast, Ca.shapes(spec), spec, mask) if out is None else Ca.check_out(out, self.num_envs, spec, self.device, rays)
+        self._sensor_launch('_last_cast_mask', mask,
+                            lambda m, stream: Ca.cast(self.cfg, self._bufs_ref, spec, rays.data_ptr(), None if ray_link is None else ray_link.data_ptr(), m, out, stream))
+        self._last_cast_rays = (rays, ray_link)  # until the stream has consumed them
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
