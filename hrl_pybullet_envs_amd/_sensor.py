@@ -1,6 +1,6 @@
-"""What the bindings of the twelve sensor libraries share (render_device.py, scan_device.py, probe_device.py, field_device.py, route_device.py,
-see_device.py, frontier_device.py, camera_device.py, links_device.py, chase_device.py, dyn_device.py, cast_device.py): the base of their spec records, the loader of a library, the checks of
-the tensors handed in (`out=`, points), and -- for the ten whose outputs are a record of optional members (all but render and scan) -- the
+"""What the bindings of the thirteen sensor libraries share (render_device.py, scan_device.py, probe_device.py, field_device.py, route_device.py,
+see_device.py, frontier_device.py, camera_device.py, links_device.py, chase_device.py, dyn_device.py, cast_device.py, closest_device.py): the base of their spec records, the loader of a library, the checks of
+the tensors handed in (`out=`, points), and -- for the eleven whose outputs are a record of optional members (all but render and scan) -- the
 namedtuple and the ctypes record made from FIELDS, the one check of `out=` and the launch."""
 import collections
 import ctypes as C

@@ -7,7 +7,8 @@ batched visibility map, include/hrl_see.h), hrl_pybullet_envs_amd/libhrl_frontie
 hrl_pybullet_envs_amd/libhrl_camera_hip.so (the batched first-person camera, include/hrl_camera.h),
 hrl_pybullet_envs_amd/libhrl_links_hip.so (the batched link states, include/hrl_links.h), hrl_pybullet_envs_amd/libhrl_chase_hip.so
 (the batched chase camera, include/hrl_chase.h), hrl_pybullet_envs_amd/libhrl_dyn_hip.so (the batched dynamics terms,
-include/hrl_dyn.h) and hrl_pybullet_envs_amd/libhrl_cast_hip.so (the batched ray test, include/hrl_cast.h): thirteen libraries.
+include/hrl_dyn.h), hrl_pybullet_envs_amd/libhrl_cast_hip.so (the batched ray test, include/hrl_cast.h) and
+hrl_pybullet_envs_amd/libhrl_closest_hip.so (the batched closest points, include/hrl_closest.h): fourteen libraries.
 
 hipcc cross-compiles for gfx950 without a GPU.  Usage: python -m hrl_pybullet_envs_amd.build [--force]
 """
@@ -42,6 +43,9 @@ CHASE = ('chase', 'libhrl_chase_hip.so', 'chase_hip.hip', 'chase_core.h', 'hrl_c
 DYN = ('dyn', 'libhrl_dyn_hip.so', 'dyn_hip.hip', 'dyn_core.h', 'hrl_dyn.h')
 # The ray test stands on the chase camera's whole chain (render, scan, camera, links, chase): its solids and their intersections.
 CAST = ('cast', 'libhrl_cast_hip.so', 'cast_hip.hip', 'cast_core.h', 'hrl_cast.h')
+# The closest points stand on the link states' specification and on the step's own narrow phase (step_core.h, included); of the chase
+# camera's chain they read the headers alone (the class bits and the hit codes).
+CLOSEST = ('closest', 'libhrl_closest_hip.so', 'closest_hip.hip', 'closest_core.h', 'hrl_closest.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O2', '-std=c++17', '-ffp-contract=off', '-fno-slp-vectorize', '-fPIC', '-shared']
 
 
@@ -177,8 +181,19 @@ def build_cast(force=False, verbose=False):
     return lib
 
 
+def build_closest(force=False, verbose=False):
+    """The closest points' library; returns its path.  It depends on everything the link states depend on, on their specification, on
+    the headers its own header includes, and on its own three files."""
+    _, lib, source, core, header = CLOSEST
+    lib = os.path.join(PKG, lib)
+    headers = ['hrl_envs.h', header, CHASE[4], CAMERA[4], LINKS[4]] + [h for *_, h in SENSORS[:2]]
+    if force or _stale(lib, [source, core, LINKS[3], 'sensor_launch.h'] + SOURCES[1:], headers):
+        _compile(lib, source, verbose)
+    return lib
+
+
 def build(force=False, verbose=False):
-    """The thirteen libraries; returns the step library's path."""
+    """The fourteen libraries; returns the step library's path."""
     if force or _stale():
         _compile(LIB, 'hrl_hip.hip', verbose)
     for name, *_ in SENSORS:
@@ -191,10 +206,11 @@ def build(force=False, verbose=False):
     build_chase(force, verbose)
     build_dyn(force, verbose)
     build_cast(force, verbose)
+    build_closest(force, verbose)
     return LIB
 
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, verbose=True))
-    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE, DYN, CAST]:
+    for _, lib, *_ in SENSORS + [ROUTE, SEE, FRONTIER, CAMERA, LINKS, CHASE, DYN, CAST, CLOSEST]:
         print(os.path.join(PKG, lib))

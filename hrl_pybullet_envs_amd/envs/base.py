@@ -272,6 +272,23 @@ class BatchedGymEnv:
         cast_device.default_spec for the frame and the classes, cast_device.lidar_rays, down_rays and from_to for the rays)."""
         return self._backend().cast(rays, spec, mask, out, ray_link)
 
+    def closest_batch(self, spec=None, mask=None, out=None):
+        """How far every body of EVERY env's robot is from everything it could collide with, in one launch: Closest(distance float32
+        [N, B, 6], which int32 [N, B, 6], on_link, on_surface and normal float32 [N, B, 6, 3]) on the env's device -- the simulator's
+        getClosestPoints for all envs: per link and per class (ground, wall, box, food, poison, self) the signed gap to the nearest
+        surface the step collides with, which one it is, the two closest points and the normal (BatchedEnv.closest;
+        closest_device.default_spec for the classes)."""
+        return self._backend().closest(spec, mask, out)
+
+    def get_closest_points(self, distance, link=None, index=0):
+        """The cells of env `index` whose gap is at most `distance` metres, as a list of tuples (link, class code, index, distance,
+        on_link, on_surface, normal) -- what `p.getClosestPoints(robot, other, distance)` answers in the reference, over every class at
+        once (closest_device.within; class codes closest_device.HIT_*; `link`: only that link, links_device.NAMES order).  One launch
+        and one copy to the host per call: for many envs read closest_batch()."""
+        from .. import closest_device as Cl
+        out = self._backend().closest()
+        return Cl.within(tuple(t[index].cpu() for t in out), distance, link)
+
     def close(self):
         if self._env is not None:
             self._env.close()

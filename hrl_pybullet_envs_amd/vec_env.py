@@ -431,6 +431,28 @@ class BatchedEnv:
         self._last_cast_rays = (rays, ray_link)  # until the stream has consumed them
         return out
 
+    def closest(self, spec=None, mask=None, out=None):
+        """How far every body of every env's robot is from everything it could collide with: a namedtuple Closest(distance float32
+        [N, B, 6], which int32 [N, B, 6], on_link, on_surface, normal float32 [N, B, 6, 3]) on this device, from ONE launch on the current
+        stream (closest_device.py, include/hrl_closest.h) -- what the simulator's getClosestPoints answers one pair at a time.  B = 13
+        links for the ants, 1 for the point bot (links_device.NAMES); the class axis is closest_device.CLASS_NAMES: ground, wall, box,
+        food, poison, self.  The surfaces are what the STEP collides with: the ground plane, the walls' inner faces (0.05 m nearer than
+        the line scan() and cast() meet), the maze box, the item cubes (indices as in scan() and cast()) and, for `self`, the capsules
+        of the other legs in the step's 48 pairs.  distance = the signed gap between the two surfaces (negative = penetration, +inf
+        where the class has no surface, was not asked for or nothing finite was found), which = class | index << 8
+        (closest_device.decode; closest_device.HIT_NONE wherever distance is +inf), on_link / on_surface = the closest points in world
+        coordinates, normal = the unit normal from the surface towards the link (zeros where nothing was found).  The point bot's cube
+        against an item cube is exact unless the nearest features are two edges, then an upper bound.  `spec`: an hrl_closest_spec
+        (closest_device.default_spec(cfg, classes)); None = every class.  Envs with mask[i] == 0 keep what `out` holds (zeros in fresh
+        tensors).  `out`: a Closest of tensors to reuse; a None member is not computed.  The answer is of the state / items tensors as
+        they are; nothing else is read or written.  Capturable: call it once before the capture."""
+        from . import closest_device as Cl
+        if spec is None:
+            spec = self._default_spec('closest', lambda: Cl.default_spec(self.cfg))
+        out = self._fresh_out(Cl, Cl.Closest, Cl.shapes(self.cfg, spec), spec, mask) if out is None else Cl.check_out(out, self.num_envs, self.cfg, spec, self.device)
+        self._sensor_launch('_last_closest_mask', mask, lambda m, stream: Cl.closest(self.cfg, self._bufs_ref, spec, m, out, stream))
+        return out
+
     def close(self):
         if getattr(self, '_h', None):
             _lib.lib().hrl_destroy(self._h)
