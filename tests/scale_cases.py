@@ -1,7 +1,8 @@
-"""Shared by tests/test_sensors_scale_host.py and tests/test_gpu_sensors_scale.py: the records of thousands of envs the seven sensors are
-checked on at the workload's size -- the fp32 oracle's states of 30 seeded steps with a fixed, sparse pattern of spread, hostile and
+"""Shared by tests/test_sensors_scale_host.py and tests/test_gpu_sensors_scale.py: the records of
+thousands of envs the sensors are checked on at the workload's size -- the fp32 oracle's states of 30 seeded steps with a fixed, sparse pattern of spread, hostile and
 hand-made envs written over them, so that neighbouring workgroups do unequal work --, one specification per sensor, and the host build
-of every sensor on those records (the device equals the oracle bit for bit, tests/test_gpu_parity.py: the whole expected side is
+of every sensor on those records: the seven of SENSORS on SHAPES, and beside them the four of LATER (the chase camera, the ray test,
+the closest points and the dynamics terms) on shapes of their own (LATER_SHAPES, DYN_CASES) (the device equals the oracle bit for bit, tests/test_gpu_parity.py: the whole expected side is
 computable without a GPU).  Test infrastructure only."""
 import collections
 import functools
@@ -9,8 +10,13 @@ import math
 
 import numpy as np
 
+import cast_cases as cac
+import chase_cases as chc
+import closest_cases as clc
+import dyn_cases as dc
 import field_cases as fc
 import frontier_cases as xc
+import links_cases as lc
 import orc
 import probe_cases as pc
 import render_cases as rc
@@ -18,6 +24,9 @@ import route_cases as rt
 import scan_cases as sc
 import see_cases as vc
 from hrl_pybullet_envs_amd import _capi as K
+from hrl_pybullet_envs_amd import cast_device as Ca
+from hrl_pybullet_envs_amd import chase_device as Ch
+from hrl_pybullet_envs_amd import closest_device as Cl
 from hrl_pybullet_envs_amd import field_device as F
 from hrl_pybullet_envs_amd import frontier_device as X
 from hrl_pybullet_envs_amd import probe_device as P
@@ -28,6 +37,15 @@ from hrl_pybullet_envs_amd import see_device as V
 SENSORS = ('render', 'scan', 'probe', 'field', 'route', 'see', 'frontier')
 KINDS = (K.HRL_ANT_GATHER, K.HRL_ANT_MAZE, K.HRL_POINT_GATHER)   # the three with BASELINE configs: items | the box and targets | the point bot
 SHAPES = ((4096, (32, 32)), (1029, (64, 64)))   # (envs, grid): the benchmark's size | the longest relaxation; 1029 = 4 * 256 + 5: no multiple of 8 XCDs or 256 CUs
+# the four sensors merged after the seven, beside them and not among them: (envs, size) per sensor -- chase: (width, height), 128 x 96 = 12
+# chunks of 1024 pixels per workgroup | cast: rays per env, 129 = two full waves and one ray, 1024 = the maximum | closest: no size
+LATER = ('chase', 'cast', 'closest', 'dyn')
+LATER_SHAPES = {'chase': ((4096, (32, 16)), (1029, (128, 96))), 'cast': ((4096, 129), (1029, 1024)), 'closest': ((4096, None), (1029, None))}
+# dyn reads the state and the model only, 16 envs per workgroup: (kind, envs, where the states come from) -- 4096 = 256 workgroups on
+# records() | 16389 = 1024 workgroups and a tail of 5 envs, hand-made states (the oracle is not stepped at that size)
+RECORDS, HAND_MADE = 'records', 'hand-made'
+DYN_CASES = ((K.HRL_ANT_GATHER, 4096, RECORDS), (K.HRL_POINT_GATHER, 4096, RECORDS), (K.HRL_ANT_GATHER, 16389, HAND_MADE))
+DYN_PLACES = (0, 4, 9, 16, 24)   # of a state record: x | a quaternion component | a joint angle | a velocity | a joint rate
 STEPS, SEED = 30, 21
 # every SPREAD_EVERY-th env (from SPREAD_AT) takes a placement of probe_cases.SPREAD, ...: three residues that never meet
 SPREAD_EVERY, SPREAD_AT = 16, 3
@@ -96,6 +114,26 @@ def records(kind, n, seed=SEED):
     return (cfg,) + frozen(st, it, aux)
 
 
+@functools.lru_cache(None)
+def hand_made_records(kind, n, seed=SEED):
+    """(cfg, state, items, aux) for n ant envs whose states are blocks of dyn_cases.hand_made(seed + k, 12) -- tilted torsos, joints at
+    and between their stops, velocities of the shards' scale --, columns 29..31, items and aux as the oracle's reset leaves them (what a
+    device env of that size holds after reset()), and every HOSTILE_EVERY-th env with a NaN in place DYN_PLACES[turn % 5]."""
+    cfg = orc.default_config(kind, **config_args(n, seed))
+    o = orc.OracleEnv(cfg, np.float32)
+    o.reset()
+    st = np.concatenate([dc.hand_made(seed + k, 12) for k in range((n + 11) // 12)])[:n].astype(np.float32)
+    st[:, 29:32] = o.state[:, 29:32]
+    for k, e in turns(n, HOSTILE_EVERY, HOSTILE_AT):
+        st[e, DYN_PLACES[k % 5]] = np.nan
+    return (cfg,) + frozen(st, o.items.copy(), o.aux.copy())
+
+
+def records_of(sensor, kind, n, size, seed=SEED):
+    """The records a case is built on: records(), but for dyn's hand-made case."""
+    return hand_made_records(kind, n, seed) if (sensor, size) == ('dyn', HAND_MADE) else records(kind, n, seed)
+
+
 def blind(state):
     """The envs whose robot has no finite place."""
     return ~np.isfinite(state[:, 0:2]).all(1)
@@ -133,6 +171,39 @@ SPECS = {'render': lambda kind, size: rc.view_of(kind, R.HRL_VIEW_EGO_HEADING, (
          'frontier': lambda kind, size: xc.spec_of(size, margin_of(kind), X.EDGE, X.KNOWN_ONLY, kind=kind)}
 
 
+def n_links(kind):
+    return 1 if kind == K.HRL_POINT_GATHER else 13
+
+
+# the four of LATER.  chase: the heading frame, the library's default orbit (3 m behind the torso, 30 degrees above it), every class, a
+# ground checker of 1 m | cast: the link frame, which reads all 13 link frames of the env from LDS, every class | closest: every class |
+# dyn: 16 sites over every link (and tau, of inputs())
+SPECS.update({'chase': lambda kind, size: chc.spec_of(size, Ch.HRL_SCAN_HEADING, Ch.HRL_EYE_TORSO, 0.0, 0.0, -30.0, 3.0, Ch.EVERYTHING, tile=1.0),
+              'cast': lambda kind, size: cac.spec_of(Ca.HRL_CAST_LINK, size, Ca.EVERYTHING),
+              'closest': lambda kind, size: clc.spec_of(Cl.EVERYTHING),
+              'dyn': lambda kind, size: dc.spec_of(lc.sixteen_sites(n_links(kind)))})
+SHARED = ('ray_link',)   # the members of a case's `extra` that all envs share: no row per env
+
+
+def cast_rays(kind, n, R, seed):
+    """(rays [n, R, 6] float32, ray_link [R] int32) in link coordinates, built at once for all envs: one seeded pattern -- a lidar of 4
+    rings x 16 from the torso (link 0), a range finder of 1 m at each foot tip (the ants), then random segments on random links up to R
+    --, the same for every env but for a seeded move of every ray's `to` by at most 0.2 m along each axis."""
+    rng = np.random.default_rng(seed)
+    parts, links = [Ca.lidar_rays(16, (-30.0, -10.0, 0.0, 15.0), 8.0, 0.3).numpy()], [np.zeros(64, np.int32)]
+    if kind != K.HRL_POINT_GATHER:
+        feet, foot_links = Ca.down_rays(1.0)
+        parts.append(feet.numpy()); links.append(foot_links.numpy())
+    fill = R - sum(len(p) for p in parts)
+    a = np.stack((rng.uniform(-2, 2, fill), rng.uniform(-2, 2, fill), rng.uniform(-0.4, 1.5, fill)), 1)
+    b = np.stack((rng.uniform(-6, 6, fill), rng.uniform(-6, 6, fill), rng.uniform(-1.0, 0.5, fill)), 1)
+    parts.append(np.concatenate((a, b), 1)); links.append(rng.integers(0, n_links(kind), fill))
+    pattern = np.concatenate(parts).astype(np.float32)
+    rays = np.ascontiguousarray(np.broadcast_to(pattern, (n, R, 6)))
+    rays[:, :, 3:6] += rng.uniform(-0.2, 0.2, (n, R, 3)).astype(np.float32)
+    return rays, np.concatenate(links).astype(np.int32)
+
+
 def see_inputs(cfg, state, seed):
     """(first, clear): the states of the first launch -- every robot moved by up to 3 m along x and y, every STILL_EVERY-th left where it
     is -- and the envs whose memory the second launch clears."""
@@ -158,8 +229,12 @@ def see_host(cfg, state, items, aux, spec, first, clear):
 
 def inputs(sensor, kind, n, size, seed=SEED):
     """What the sensor is handed besides the records and its spec, as a dict of arrays with one row per env."""
-    cfg, st, it, aux = records(kind, n, seed)
+    cfg, st, it, aux = records_of(sensor, kind, n, size, seed)
     spec = SPECS[sensor](kind, size)
+    if sensor == 'cast':
+        return dict(zip(('rays', 'ray_link'), cast_rays(kind, n, size, 31 + kind)))
+    if sensor == 'dyn':
+        return dict(tau=dc.taus(cfg, n))
     if sensor == 'probe':
         return dict(points=pc.draw_points(cfg, st, spec.frame, spec.n_points, pc.seed_of(cfg, spec)))
     if sensor == 'route':
@@ -195,13 +270,21 @@ def host_build(sensor, cfg, state, items, aux, spec, extra):
         return rt.route_host(cfg, state, items, aux, spec, extra['starts'])
     if sensor == 'see':
         return see_host(cfg, state, items, aux, spec, extra['first'], extra['clear'])
+    if sensor == 'chase':
+        return chc.chase_host(cfg, state, items, aux, spec)
+    if sensor == 'cast':
+        return cac.cast_host(cfg, state, items, aux, spec, extra['rays'], extra['ray_link'])
+    if sensor == 'closest':
+        return clc.closest_host(cfg, state, items, aux, spec)
+    if sensor == 'dyn':
+        return dc.dyn_host(cfg, state, spec, tau=extra['tau'])
     return xc.frontier_host(cfg, state, items, aux, spec, np.ascontiguousarray(extra['seen']))
 
 
 def host_build_rows(sensor, case, rows):
     """host_build of the envs `rows` (a slice) of a case alone, as a shard of their own."""
     st, it, aux = (np.ascontiguousarray(a[rows]) for a in (case.state, case.items, case.aux))
-    return host_build(sensor, sub_config(case.cfg, len(st)), st, it, aux, case.spec, {k: np.ascontiguousarray(v[rows]) for k, v in case.extra.items()})
+    return host_build(sensor, sub_config(case.cfg, len(st)), st, it, aux, case.spec, {k: v if k in SHARED else np.ascontiguousarray(v[rows]) for k, v in case.extra.items()})
 
 
 def members(out):
@@ -215,12 +298,48 @@ Case = collections.namedtuple('Case', 'cfg state items aux spec extra want')
 @functools.lru_cache(None)
 def expected(sensor, kind, n, size, seed=SEED):
     """The case of (sensor, kind, batch shape): records, spec, further inputs and the host build's outputs (computed once, read-only)."""
-    cfg, st, it, aux = records(kind, n, seed)
+    cfg, st, it, aux = records_of(sensor, kind, n, size, seed)
     spec, extra = SPECS[sensor](kind, size), inputs(sensor, kind, n, size, seed)
     frozen(*extra.values())
     want = host_build(sensor, cfg, st, it, aux, spec, extra)
     frozen(*members(want))
     return Case(cfg, st, it, aux, spec, extra, want)
+
+
+def later_cases():
+    """(sensor, kind, envs, size) of every case of the four of LATER."""
+    out = [(s, kind, n, size) for s in LATER[:3] for kind in KINDS for n, size in LATER_SHAPES[s]]
+    return out + [('dyn', kind, n, source) for kind, n, source in DYN_CASES]
+
+
+# ------------------------------------------------------------------------------------------------ the comparison at scale
+def host_rows(want):
+    """Every output of a host build as bytes [n, bytes per env]."""
+    return [np.ascontiguousarray(w).reshape(len(w), -1).view(np.uint8) for w in want]
+
+
+def nan_for_nan(rows):
+    """Rows of float32 as bytes with every NaN replaced by one NaN: the payload and the sign of a NaN are the processor's own (dyn's
+    hostile envs; tests/test_gpu_dyn.py and tests/test_gpu_links_scale.py hold a NaN against a NaN likewise)."""
+    out = []
+    for r in rows:
+        f = np.array(r).view(np.float32)
+        f[np.isnan(f)] = np.float32(np.nan)
+        out.append(f.view(np.uint8))
+    return out
+
+
+def differences(names, got, want, envs=None):
+    """The first few (output, env, byte within the env's row, env % 8) where two lists of [rows, bytes] arrays differ (`envs`: the env
+    of each row; None: row i is env i), and how the wrong envs fall on the eight residues (a pattern by XCD or by place in the batch
+    shows here)."""
+    first, by_residue = [], np.zeros(8, int)
+    for name, g, w in zip(names, got, want):
+        bad = np.nonzero((g != w).any(1))[0]
+        ids = bad if envs is None else envs[bad]
+        by_residue += np.bincount(ids % 8, minlength=8)
+        first += [(name, int(e), int(np.nonzero(g[r] != w[r])[0][0]), int(e % 8)) for r, e in zip(bad[:4], ids[:4])]
+    return dict(first=first, wrong_envs=int(by_residue.sum()), wrong_envs_by_residue=by_residue.tolist())
 
 
 # ------------------------------------------------------------------------------------------------ what the records reach
@@ -239,6 +358,24 @@ def reached(sensor, kind, n, size, seed=SEED):
     on these)."""
     c = expected(sensor, kind, n, size, seed)
     w, dead = c.want, blind(c.state)
+    if sensor in ('chase', 'cast'):   # seg [n, ...]: class | index << 8 | face << 16; the robot's index is the link
+        seg = w.seg.reshape(n, -1)
+        robot = (seg & 255) == Ch.HIT_ROBOT
+        out = dict(classes=classes(seg), links=set(np.unique((seg[robot] >> 8) & 255).tolist()), robot_envs=int(robot.any(1).sum()), blind=int(dead.sum()))
+        if sensor == 'cast':
+            out.update(hits=int((seg != 0).sum()), misses=int((seg == 0).sum()), blind_hits=int((seg[dead] != 0).sum()))
+        return out
+    if sensor == 'closest':
+        d = w.distance
+        return dict(finite=np.isfinite(d).sum((0, 1)).tolist(), negative=(d < 0).sum((0, 1)).tolist(), none=(d == np.inf).sum((0, 1)).tolist(), nan=int(np.isnan(d).sum()),
+                    blind=int(dead.sum()), blind_cells=int(np.isfinite(d[dead]).sum()))
+    if sensor == 'dyn':
+        hostile = np.zeros(n, bool)
+        hostile[HOSTILE_AT::HOSTILE_EVERY] = True
+        finite = {name: np.isfinite(a.reshape(n, -1)).all(1) for name, a in zip(dc.NAMES, w)}
+        every = np.logical_and.reduce(list(finite.values()))
+        return dict(hostile=int(hostile.sum()), hostile_not_finite=int((hostile & ~every).sum()), hostile_bias_or_accel=int((hostile & ~(finite['bias'] & finite['accel'])).sum()),
+                    others_not_finite=int((~hostile & ~every).sum()))
     if sensor == 'render':
         return dict(colours=colours(w))
     if sensor == 'scan':

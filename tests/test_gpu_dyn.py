@@ -1,5 +1,5 @@
 """The batched dynamics terms on the MI355X (csrc/dyn_hip.hip, include/hrl_dyn.h) against the host build of their specification
-(tests/dyn_host, csrc/dyn_core.h), bit for bit in all seven outputs, and their surface: tau, None members, masks, streams, `out=`, the gym
+(tests/dyn_host, csrc/dyn_core.h), bit for bit in all seven outputs, and their surface: tau, None members, masks, streams and graph replay, `out=`, the gym
 classes' dynamics_batch(), and that the step does not notice them.  At most 1029 envs per test."""
 import numpy as np
 import pytest
@@ -144,6 +144,51 @@ def test_dynamics_follow_the_stream():
     torch.cuda.synchronize()
     assert same(dev, dc.dyn_host(env.cfg, env.state.cpu().numpy(), spec, tau=tau.cpu().numpy()))
     env.close()
+
+
+def test_dynamics_replay_in_a_graph():
+    """The single launch captured once (the first call ran before the capture, on a side stream; `out=` and `tau` are tensors allocated
+    once, whose pointers the captured launch holds) and replayed after each of three eager steps, the next action's torques written
+    into `tau` in place before each replay, gives the answers of an eager twin bit for bit.  The graph is one launch: no branches."""
+    kind, n = K.HRL_ANT_GATHER, 17
+    spec = dc.spec_of(lc.sixteen_sites(13))
+    acts = torch.rand(5, n, 8, device='cuda', generator=torch.Generator(device='cuda').manual_seed(5)) * 2 - 1
+    fresh_out = lambda cfg: Dy.Dynamics(*(torch.zeros((n,) + shape, device='cuda') for shape in Dy.shapes(cfg, spec)))
+    eager, eager_answers = make_env(kind, n), []
+    eager.reset()
+    eout = fresh_out(eager.cfg)
+    for r in range(4):
+        eager.step(acts[r])
+        eager.dynamics(spec, tau=Dy.torques(eager.cfg, acts[r + 1]), out=eout)
+        eager_answers.append(Dy.Dynamics(*(x.clone() for x in eout)))
+    env = make_env(kind, n)
+    env.reset()
+    out, tau = fresh_out(env.cfg), torch.zeros(n, 14, device='cuda')
+    ptrs = [x.data_ptr() for x in out] + [tau.data_ptr()]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):   # the warm-up torch asks for; the library's constants are uploaded here, outside the capture
+        env.step(acts[0])
+        tau.copy_(Dy.torques(env.cfg, acts[1]))
+        env.dynamics(spec, tau=tau, out=out)
+        first = Dy.Dynamics(*(x.clone() for x in out))
+    torch.cuda.current_stream().wait_stream(side)
+    assert same(first, eager_answers[0]) and bool(torch.isfinite(first.accel).all()) and bool(first.accel.any())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        env.dynamics(spec, tau=tau, out=out)
+    for r in range(1, 4):
+        env.step(acts[r])
+        tau.copy_(Dy.torques(env.cfg, acts[r + 1]))
+        g.replay()
+        assert same(out, eager_answers[r]), r
+    assert [x.data_ptr() for x in out] + [tau.data_ptr()] == ptrs
+    assert not same(eager_answers[1], eager_answers[3])   # the robots moved and the torques changed: the answers are not the same
+    assert not torch.equal(eager_answers[1].accel, eager_answers[3].accel) and not torch.equal(eager_answers[1].mass, eager_answers[3].mass)
+    torch.cuda.synchronize()
+    assert torch.equal(env.state, eager.state)
+    del g
+    env.close(); eager.close()
 
 
 def test_out_is_reused_and_checked():
